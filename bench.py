@@ -1,7 +1,7 @@
 """
 bench.py -- ELBO steps/sec on the block-tri-diagonal Gauss-Markov path.
 
-  python bench.py --gpus N --steps K --warmup W [--config headline|c1|c2|c3|c5]
+  python bench.py --gpus N --steps K --warmup W [--config headline|c1|c2|c3|c5] [--full] [--dump-outputs DIR]
       N > 1: either the caller starts the N ranks (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...), or,
       when no torch.distributed environment is present, bench.py starts them itself as a child job and relays rank 0's line.
 
@@ -16,9 +16,17 @@ The other configs are BASELINE.json's `configs` (SURVEY.md 8d recipes), same JSO
     c3  double-well SDE, VDP model (VariationalMarkovGP), T = 50 000, d = 6, 64 trajectories per GPU (c4 = c3 with --gpus 8)
     c5  Sum-of-Matern kernel d = 16, 200 000 inducing states, 400 000 observations: SparseCVIGaussianProcess.update_sites(); classic_elbo()
 
-Prints ONE JSON line (rank 0) with the contract fields plus
-  roofline     : the dominant kernel timed alone with HIP events on its stream (other_kernels: the rest of the level-0 sweeps)
-  cpu_baseline : the CPU port / oracle of the same step on the host cores, bounded sample, N = 1 only
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run sets up, warms up, times the K steps and prints the line, nothing
+more.  With --full the line also holds
+  roofline      : the dominant kernel timed alone with HIP events on its stream (other_kernels: the rest of the level-0 sweeps)
+  cpu_baseline  : the CPU port / oracle of the same step on the host cores, bounded sample, N = 1 only
+  vdp           : the VDP step on the headline's trajectories (headline, N = 1)
+  other_configs : short runs of c1, c2, c3, c5 and the headline on dense naturals (headline, N = 1)
+(--no-cpu-baseline, --no-vdp, --no-other-configs leave parts of it out).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path computed in its last step as DIR/<name>.npy (float64):
+the ELBO and the model arrays a caller of the step receives; arrays of more than 2^20 elements are replaced by a fixed, seeded sample
+of their rows (dump_outputs).  The inputs depend on the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -58,6 +66,35 @@ def launch_ranks(n):
     sys.exit(0)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level parameters)
+
+DUMP_MAX_ELEMS = 1 << 20        # --dump-outputs: elements kept per array (8 MB of float64); larger arrays are row-sampled
+DUMP_MAX_BYTES = 64 << 20       # all arrays of one dump together
+DUMP_SEED = 71892305            # the row sample of an array depends on its shape alone
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write each array of `arrays` (name -> tensor / number) as dirname/<name>.npy in float64.  An array of more than
+    DUMP_MAX_ELEMS elements is replaced by a fixed, seeded sample of its leading-axis rows, in increasing row order (the same rows in
+    every run of the same arguments).  Nothing is written when the arrays exceed DUMP_MAX_BYTES together.  Call after the timed
+    steps: this synchronises with the device."""
+    import torch
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+        a = a.reshape(1) if a.dim() == 0 else a
+        if a.numel() > DUMP_MAX_ELEMS:
+            if a.numel() // a.shape[0] > DUMP_MAX_ELEMS:
+                a = a.reshape(-1)
+            keep = DUMP_MAX_ELEMS // (a.numel() // a.shape[0])
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep, replace=False))
+            a = a[torch.from_numpy(rows).to(a.device)]
+        out[name] = np.ascontiguousarray(a.to(torch.float64).cpu().numpy())
+    total = sum(x.nbytes for x in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), x)
 
 
 def obs_chol(d, noise):
@@ -285,6 +322,12 @@ class Harness:
         el = time.perf_counter() - t0
         return float(self.vdist.allreduce_max_(torch.tensor([el], dtype=torch.float64, device=self.device)).item())
 
+    def dump(self, arrays):
+        """--dump-outputs, rank 0: arrays() -> {name: array} of the last timed step, written by dump_outputs (called right after
+        the timed steps, before anything else touches the model)."""
+        if self.args.dump_outputs and self.rank == 0:
+            dump_outputs(self.args.dump_outputs, arrays())
+
     @staticmethod
     def timed(fn, reps=20):
         """average milliseconds of fn() by HIP events on torch's current stream (the stream the library launches on)"""
@@ -342,21 +385,28 @@ def bench_vdp(h, data_rank):
     def step():
         m.update_lagrange_and_param(state["mS"], lr=0.01)
         state["mS"] = m._forward_packed()
-        if state["first"] is None:
+        if state["first"] is None and a.full:
             state["first"] = m.elbo_per_trajectory(state["mS"]).clone()      # parity probe against the C port's first step
         state["e"] = h.vdist.allreduce_sum_(m.elbo(state["mS"]))
 
     elapsed = h.run(step)
+    pl = m.plan
+    # the posterior marginals (m_t, S_t) and the drift parameters (A_t, b_t) the step leaves, unpacked to [B T, ...] (time-major per
+    # trajectory, independent of the partition)
+    h.dump(lambda: {"elbo": state["e"],
+                    "m": pl.unpack(vidp_amd.VEC, state["mS"][0]).reshape(B * T, d),
+                    "S": pl.unpack(vidp_amd.SYM, state["mS"][1]).reshape(B * T, d, d),
+                    "A": pl.unpack(vidp_amd.FULL, m.A, T - 1).reshape(B * (T - 1), d, d),
+                    "b": pl.unpack(vidp_amd.VEC, m.b, T - 1).reshape(B * (T - 1), d)})
     m.plan.check_info()
     e = float(state["e"])
     assert np.isfinite(e), "non-finite VDP ELBO"
-    pl = m.plan
     out = h.line(elapsed, f"VDP (VariationalMarkovGP) inference step (update_lagrange + update_param, forward_pass, elbo) on double-well SDE "
                           f"trajectories, T={T}, d={d}, {B} trajectories per GPU, stabilize_system on", "c3",
                  {"trajectories_per_gpu": B, "T": T, "d": d, "total_trajectories": B * h.world,
                   "partition": {"levels": pl.nlevels, "segment_len": pl.R, "lanes": pl.Lpad}})
     out["elbo_last"] = e
-    if h.rank == 0:
+    if h.rank == 0 and a.full:
         # the final Lagrange sweep (psi, lambda by the partitioned affine recurrence, then the update of (A, b) node by node) alone,
         # on scratch copies of (A, b): the kernel with the largest share of the step
         lib = vidp_amd._lib.load()
@@ -419,11 +469,12 @@ def bench_cvigp(h, data_rank):
     def step():
         m.update_sites()
         e_loc = m.elbo()
-        if len(firsts) < 2:
+        if len(firsts) < 2 and a.full:
             firsts.append(e_loc.clone())                 # this rank's own chain, for the parity probe against the C port
         state["e"] = h.vdist.allreduce_sum_(e_loc)
 
     elapsed = h.run(step)
+    h.dump(lambda: {"elbo": state["e"], "site_nat1": m.sites.nat1, "site_nat2": m.sites.nat2})
     e = float(state["e"])
     assert np.isfinite(e), "non-finite ELBO"
     pl = m.dist_p.plan
@@ -431,7 +482,7 @@ def bench_cvigp(h, data_rank):
                  "c2", {"trajectories_per_gpu": 1, "T": T, "d": d, "total_trajectories": h.world,
                         "partition": {"levels": pl.nlevels, "segment_len": pl.R, "lanes": pl.Lpad}})
     out["elbo_last"] = e
-    if h.rank == 0:
+    if h.rank == 0 and a.full:
         lib = vidp_amd._lib.load()
         ssm = m.dist_p
         pr, b = ssm._precision_packed(), ssm._kf_cache["bufs"]
@@ -509,6 +560,8 @@ def bench_sparse(h, data_rank):
         state["e"] = m.classic_elbo((t, y))              # shared: already the sum over the ranks
 
     elapsed = h.run(step)
+    # the sites (rank 0's range of inducing states when the chain is shared)
+    h.dump(lambda: {"elbo": state["e"], "site_nat1": m.nat1, "site_nat2": m.nat2})
     pl = m._shard.plan if shared else m.dist_p.plan
     pl.check_info()
     e = float(state["e"])
@@ -525,7 +578,7 @@ def bench_sparse(h, data_rank):
                                         f"factorisation), edge sites all-gathered ({m.nat1.shape[-1] + m.nat2.shape[-1] ** 2} doubles per rank), "
                                         f"4 ELBO scalars all-reduced; rank 0 owns inducing states [{sh.node_lo}, {sh.node_hi})")
     out["elbo_last"] = e
-    if h.rank == 0 and not shared:
+    if h.rank == 0 and not shared and a.full:
         # the level-0 kernels of the MFMA sweeps alone (mfgm_wide_stage), on the model's own arrays, in the form the model uses
         lib = vidp_amd._lib.load()
         m._marginals()
@@ -688,7 +741,7 @@ def bench_cvidp(h, data_rank):
     def step():
         model.update_data_sites(args.lr_data)
         model.update_girsanov_sites(args.lr_girsanov)
-        if not first_elbo:
+        if not first_elbo and args.full:
             e_traj = model.classic_elbo_per_trajectory()     # the parity probe against the C port's first step
             first_elbo.append(e_traj.clone())
             e = e_traj.sum()
@@ -711,6 +764,10 @@ def bench_cvidp(h, data_rank):
     fence()
     elapsed = time.perf_counter() - t0
     elapsed = float(vdist.allreduce_max_(torch.tensor([elapsed], dtype=torch.float64, device=device)).item())
+    # the ELBO (summed over trajectories and ranks), the posterior marginals at the observation times that the ELBO's variational
+    # expectation used and the data sites, [B n_obs, ...] in trajectory-major order
+    h.dump(lambda: {"elbo": elbos[-1], "fx_mus_obs": model.fx_mus_obs, "fx_covs_obs": model.fx_covs_obs,
+                    "data_nat1": model.data_nat1, "data_nat2": model.data_nat2})
     plan.check_info()
     elbo_vals = [float(e.item()) for e in elbos]
     assert all(np.isfinite(elbo_vals)), "non-finite ELBO"
@@ -726,7 +783,10 @@ def bench_cvidp(h, data_rank):
         "elbo_last": elbo_vals[-1],
     }
 
-    if rank == 0:
+    trainer = rank == 0 and getattr(args, "through_trainer", False) and args.config in ("headline", "c1")
+    if trainer and not args.full:
+        out["trainer"] = trainer_rate(model, args)      # asked for by name: runs without --full as well
+    if rank == 0 and args.full:
         # ---- roofline: every level-0 sweep kernel of the step timed alone; the one with the largest share of the step is reported --
         lib = vidp_amd._lib.load()
         from vidp_amd.packed import _ptr, _stream
@@ -871,8 +931,8 @@ def bench_cvidp(h, data_rank):
             coarse_b = timed(coarse_selinv)
             out["roofline"]["step"].update(coarse_factor_ms_per_refresh=coarse_f, coarse_backward_ms_per_refresh=coarse_b,
                                            coarse_levels_share_of_step=2 * (coarse_f + coarse_b) / ms_per_step)
-        if getattr(args, "through_trainer", False) and args.config in ("headline", "c1"):
-            out["trainer"] = trainer_rate(model, args)
+        if trainer:
+            out["trainer"] = trainer_rate(model, args)  # after the roofline, which times kernels on the state the timed steps left
         if world == 1 and not args.no_vdp and args.config == "headline":
             # free the CVI-DP state first: the VDP model keeps its own ~15 GB resident
             del model, f, s, cand, cq
@@ -915,7 +975,7 @@ def trainer_rate(model, args):
 
 def other_configs(args, harness, data_rank):
     """BASELINE.json's other configurations, each as a short run of the same contract (value, ms_per_step, roofline, cpu_baseline), so
-    that the driver's one default invocation records them all: c1 (the reference's CPU-runnable case), c2, c3 and c5 on one GPU."""
+    that one --full invocation records them all: c1 (the reference's CPU-runnable case), c2, c3 and c5 on one GPU."""
     import copy
     import gc
     import torch
@@ -925,6 +985,7 @@ def other_configs(args, harness, data_rank):
         a.config, a.steps, a.warmup, a.no_vdp = name, args.other_steps, 2, True
         a.B, a.T, a.d, a.lr_data, a.lr_girsanov = 64, 100000, 6, 0.5, 0.1      # (c1 / c3 set their own sizes)
         a.dense = a.through_trainer = False
+        a.dump_outputs = None                   # the dump is the headline's
         if name == "headline_dense":
             # the headline workload on the dense-naturals route (no cq state): the path of every model without that structure
             a.config, a.dense, a.no_cpu_baseline = "headline", True, True
@@ -944,8 +1005,12 @@ def other_configs(args, harness, data_rank):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: roofline, CPU baseline, VDP step, other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--B", type=int, default=64, help="trajectories per GPU")
     ap.add_argument("--T", type=int, default=100000)
     ap.add_argument("--d", type=int, default=6)
@@ -955,7 +1020,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-vdp", action="store_true", help="skip the secondary VDP step measurement")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="headline run only: do not append the short runs of BASELINE.json's other configurations (other_configs)")
+                    help="with --full: do not append the short runs of BASELINE.json's other configurations (other_configs)")
     ap.add_argument("--dense", action="store_true", help="CVI-DP on the dense-naturals route (the cq state off, as VIDP_CQ=0)")
     ap.add_argument("--through-trainer", action="store_true",
                     help="also time the loop through CVISitesTrainer (cvi_dp_trainer.py:63-95) on the same model: `trainer` in the line")
@@ -968,6 +1033,8 @@ def main():
                     help="generate the synthetic trajectories of this rank (default: the process's own rank); lets a single-rank run "
                          "reproduce one shard of a multi-rank run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus)          # does not return
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -992,7 +1059,7 @@ def main():
     harness = Harness(args, rank, world, device, dist, vdist)
     fn = bench_cvidp if args.config in ("headline", "c1") else OTHER_CONFIGS[args.config]
     out = fn(harness, data_rank)
-    if rank == 0 and world == 1 and args.config == "headline" and not args.no_other_configs:
+    if rank == 0 and world == 1 and args.config == "headline" and args.full and not args.no_other_configs:
         out["other_configs"] = other_configs(args, harness, data_rank)
     if rank == 0:
         print(json.dumps(out))

@@ -1863,6 +1863,62 @@ def test_bench_gpus_2_launches_two_ranks(amd):
     np.testing.assert_allclose(two["elbo_last"], sum(s["elbo_last"] for s in singles), rtol=1e-12)
 
 
+def test_bench_dump_outputs_repeat(amd, tmp_path):
+    """`python bench.py --dump-outputs DIR` (small headline workload): the last step's ELBO, observation marginals and data sites as
+    float64 .npy files whose ELBO is the line's elbo_last, and two runs with the same arguments write identical arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = {"elbo", "fx_mus_obs", "fx_covs_obs", "data_nat1", "data_nat2"}
+    got = []
+    for run in ("a", "b"):
+        out = str(tmp_path / run)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--B", "4",
+                            "--T", "2000", "--dump-outputs", out], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 2 and "roofline" not in line and "other_configs" not in line
+        arrays = {n[:-4]: np.load(os.path.join(out, n)) for n in os.listdir(out)}
+        assert set(arrays) == names and all(a.dtype == np.float64 for a in arrays.values())
+        assert arrays["fx_mus_obs"].shape == (4 * 39, 6) and arrays["data_nat2"].shape == (4 * 39, 6, 6)
+        assert arrays["elbo"].shape == (1,) and arrays["elbo"][0] == line["elbo_last"]
+        got.append(arrays)
+    for n in names:
+        np.testing.assert_array_equal(got[0][n], got[1][n])
+
+
+@pytest.mark.parametrize("config,extra,shapes", [
+    ("c2", [], {"site_nat1": (100000, 1), "site_nat2": (100000, 1, 1)}),
+    # c3 unpacks the partitioned arrays: the marginals over all B T nodes, the drift parameters over the B (T - 1) transitions
+    ("c3", ["--B", "2"], {"m": (2 * 50000, 6), "S": (29127, 6, 6), "A": (29127, 6, 6), "b": (2 * 49999, 6)}),
+    ("c5", ["--c5-M", "2000"], {"site_nat1": (2001, 32), "site_nat2": (1024, 32, 32)})], ids=["c2", "c3", "c5"])
+def test_bench_dump_outputs_other_configs(amd, tmp_path, config, extra, shapes):
+    """`python bench.py --config c2|c3|c5 --dump-outputs DIR`: the arrays each configuration writes, in float64, finite, the ELBO equal
+    to the line's elbo_last; the symmetric blocks (c3's marginal covariances, c5's site precisions) come out symmetric, i.e. unpacked in
+    the right layout."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / config)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", config, "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", out] + extra, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    arrays = {n[:-4]: np.load(os.path.join(out, n)) for n in os.listdir(out)}
+    assert {n: a.shape for n, a in arrays.items()} == dict(shapes, elbo=(1,))
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["elbo"][0] == line["elbo_last"]
+    for n in ("S", "site_nat2"):
+        if n in arrays and arrays[n].shape[-1] > 1:
+            np.testing.assert_allclose(arrays[n], np.swapaxes(arrays[n], -1, -2), rtol=0, atol=1e-12 * np.abs(arrays[n]).max())
+    if config == "c3":
+        assert np.all(np.linalg.eigvalsh(arrays["S"]) > 0)
+
+
 def test_bench_c5_gpus_2_is_one_shared_chain(amd):
     """`python bench.py --config c5 --gpus 2`: config 5 as BASELINE states it -- ONE chain shared between the ranks (gloo on the one GPU
     here), strong scaling -- and its ELBO equals the single-GPU run's on the same chain."""

@@ -119,6 +119,45 @@ def test_bench_refuses_a_mislabelled_world_size():
     assert r.returncode == 2 and "refusing" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_refuses_zero_steps():
+    """`--steps` is the number of timed steps and ms_per_step divides by it: 0 is an argument error, before the GPU is touched."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
+
+
+def test_bench_dump_outputs_sampling(tmp_path):
+    """bench.dump_outputs: small arrays are written whole in float64; an array above the element cap is replaced by the same seeded
+    sample of its rows in every call (in row order), and the total size of one dump is bounded."""
+    import bench
+    big = torch.arange(3 * bench.DUMP_MAX_ELEMS, dtype=torch.float64).reshape(-1, 6)
+    small = torch.arange(12, dtype=torch.float32).reshape(4, 3)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"scalar": torch.tensor(2.5, dtype=torch.float64), "small": small, "big": big})
+    s = np.load(tmp_path / "a" / "scalar.npy")
+    assert s.dtype == np.float64 and s.shape == (1,) and s[0] == 2.5
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "small.npy"), small.numpy().astype(np.float64))
+    ba, bb = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert ba.dtype == np.float64 and ba.shape[1] == 6 and ba.size <= bench.DUMP_MAX_ELEMS and ba.shape[0] == bench.DUMP_MAX_ELEMS // 6
+    np.testing.assert_array_equal(ba, bb)
+    rows = ba[:, 0] / 6
+    assert np.all(np.diff(rows) > 0) and np.all(rows == np.round(rows))
+    np.testing.assert_array_equal(ba, big.numpy()[rows.astype(np.int64)])
+    # one row above the cap: the array is sampled element-wise
+    wide = torch.arange(2 * (bench.DUMP_MAX_ELEMS + 5), dtype=torch.float64).reshape(2, -1)
+    bench.dump_outputs(str(tmp_path / "w"), {"wide": wide})
+    w = np.load(tmp_path / "w" / "wide.npy")
+    assert w.shape == (bench.DUMP_MAX_ELEMS,) and np.all(np.diff(w) > 0)
+    np.testing.assert_array_equal(w, wide.numpy().reshape(-1)[w.astype(np.int64)])
+    # over the total: an error, and nothing written
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "c"), {f"x{i}": big for i in range(9)})
+    assert not (tmp_path / "c").exists()
+
+
 def test_one_chain_exchange_volume_at_config5():
     """SURVEY 8e / config 5 (one chain, T = 200 000, d = 16, 8 ranks): the only per-time-step data that crosses ranks is the input of
     the exchange level of the partition -- n_X x (3 d^2 + 2 d) doubles with n_X = 32 (the highest level with at least 4 nodes per rank,

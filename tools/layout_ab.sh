@@ -6,7 +6,7 @@ mkdir -p $O
 for rep in 1 2 3; do
     for lib in "$@"; do
         n=$(basename $lib .so)
-        MFGM_LIB=$R/$lib python3 $R/bench.py --no-cpu-baseline --no-vdp --no-other-configs > $O/${n}_$rep.json 2>/dev/null
+        MFGM_LIB=$R/$lib python3 $R/bench.py --full --no-cpu-baseline --no-vdp --no-other-configs > $O/${n}_$rep.json 2>/dev/null
         python3 - "$O/${n}_$rep.json" "$n" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read())
