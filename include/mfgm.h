@@ -721,6 +721,29 @@ int mfgm_batched_cholesky(int N, int d, const double* A, double* L, int* info, v
  * lbatch = N or 1 (one factor shared by the whole batch).  X may alias B. */
 int mfgm_batched_trsm(int N, int d, int m, int lbatch, const double* L, const double* B, double* X, int mode, void* stream);
 
+/* ---- simulation of the SDE priors: a counter-based normal stream and Euler-Maruyama -------------------------------------------
+ * Normal stream (replaces tf.random.normal in markovflow/sde/sde_utils.py:66; the same contract is restated in DESIGN.md and, bit for
+ * bit, in the tests):
+ *   Philox4x32-10 (Salmon et al., SC'11; M0 = 0xD2511F53, M1 = 0xCD9E8D57, W0 = 0x9E3779B9, W1 = 0xBB67AE85)
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (j, k, i, s): j the pair index within a step, k the step, i the path, s the stream tag (0 = Euler-Maruyama increments;
+ *             other tags are reserved for later samplers)
+ *   output words w0..w3 -> u1 = (((w1 << 21) | (w0 >> 11)) + 0.5) * 2^-53, u2 = (((w3 << 21) | (w2 >> 11)) + 0.5) * 2^-53, both
+ *             evaluated in fp64 (the 53-bit integer converts exactly; u in (0, 1], never 0)
+ *   Box-Muller: z[i, k, 2j] = r cos(2 pi u2), z[i, k, 2j + 1] = r sin(2 pi u2), r = sqrt(-2 log u1); for odd d the last sine is dropped.
+ * A path's noise depends on (seed, i, k) only: not on the batch size, the launch shape or the order of the paths.
+ *
+ * out [P, K, d] = z[i, k, :] for paths i < P, steps k < K (the tensor the Euler-Maruyama kernel consumes with s = 0, K = N - 1). */
+int mfgm_normal_fill(unsigned long long seed, unsigned int s, int P, int K, int d, double* out, void* stream);
+/* Euler-Maruyama (sde_utils.py:36-96, with the reference's time alignment): t_{-1} = 0, dt_k = t_k - t_{k-1},
+ *   X[:, 0] = x0,  X[:, k+1] = X[:, k] + f(X[:, k]) dt_k + sqrt(dt_k) L z[:, k]   (k = 0 .. N-2; the reference's last scan step is dropped)
+ * x0 [B, d], time_grid [N] (non-decreasing, t_0 >= 0: checked by the caller), X [B, N, d] (device); L: HOST array [d, d], row-major,
+ * the lower Cholesky factor of the diffusion matrix q (upper triangle ignored).  drift: kind, d, nh and theta of the quadrature drift
+ * block are read (kinds 10 .. 15 as above; d <= 8, d = 2 for kind 10, 3 nh + 1 <= MFGM_QUAD_NTHETA for kind 11); its quadrature
+ * fields are ignored.  Noise: the stream above with tag 0. */
+int mfgm_euler_maruyama(const mfgm_quad_drift* drift, int B, int N, const double* x0, const double* time_grid, const double* L,
+                        unsigned long long seed, double* X, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

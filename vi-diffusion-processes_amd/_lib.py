@@ -134,6 +134,9 @@ EXPORTS = {
     "mfgm_plan_shard_left_marginal": (ctypes.c_int, [ctypes.c_void_p] * 5),
     "mfgm_batched_cholesky": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4),
     "mfgm_batched_trsm": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p]),
+    "mfgm_normal_fill": (ctypes.c_int, [ctypes.c_ulonglong, ctypes.c_uint] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2),
+    "mfgm_euler_maruyama": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3
+                            + [ctypes.c_ulonglong] + [ctypes.c_void_p] * 2),
 }
 
 
