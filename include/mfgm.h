@@ -726,8 +726,8 @@ int mfgm_batched_trsm(int N, int d, int m, int lbatch, const double* L, const do
  * bit, in the tests):
  *   Philox4x32-10 (Salmon et al., SC'11; M0 = 0xD2511F53, M1 = 0xCD9E8D57, W0 = 0x9E3779B9, W1 = 0xBB67AE85)
  *   key     = (seed & 0xffffffff, seed >> 32)
- *   counter = (j, k, i, s): j the pair index within a step, k the step, i the path, s the stream tag (0 = Euler-Maruyama increments;
- *             other tags are reserved for later samplers)
+ *   counter = (j, k, i, s): j the pair index within a step, k the step, i the path, s the stream tag (0 = Euler-Maruyama increments,
+ *             1 = posterior draws, 2 = prior draws at the joint time points of a conditional process; see mfgm_packed_sample)
  *   output words w0..w3 -> u1 = (((w1 << 21) | (w0 >> 11)) + 0.5) * 2^-53, u2 = (((w3 << 21) | (w2 >> 11)) + 0.5) * 2^-53, both
  *             evaluated in fp64 (the 53-bit integer converts exactly; u in (0, 1], never 0)
  *   Box-Muller: z[i, k, 2j] = r cos(2 pi u2), z[i, k, 2j + 1] = r sin(2 pi u2), r = sqrt(-2 log u1); for odd d the last sine is dropped.
@@ -743,6 +743,25 @@ int mfgm_normal_fill(unsigned long long seed, unsigned int s, int P, int K, int 
  * fields are ignored.  Noise: the stream above with tag 0. */
 int mfgm_euler_maruyama(const mfgm_quad_drift* drift, int B, int N, const double* x0, const double* time_grid, const double* L,
                         unsigned long long seed, double* X, void* stream);
+
+/* ---- seeded draws from a factorised Gauss-Markov distribution (posterior sampling) ---------------------------------------------------
+ * Contract: a draw from the distribution with precision Lambda and mean mu = Lambda^{-1} r is
+ *      x = mu + L^{-T} eps = L^{-T} (y + eps),     y = L^{-1} r,
+ * where L is the natural-order block Cholesky factor of Lambda that a form-0 factorisation exposes (mfgm_packed_factor_form with
+ * form 0; G = L_{t+1,t} stored).  L is unique, so a draw does not depend on the partition beyond rounding.  eps for sample n, chain b,
+ * node t is z[i = n, k = b T + t, :] of the normal stream above with the caller's tag s -- exactly mfgm_normal_fill(seed, s, S, B T, d)
+ * viewed as [S, B, T, d], odd d following the stream's rule.  Tag 1 is for posterior draws, tag 2 for the prior draw at the joint
+ * time points of a conditional process.  Consequences: a draw of S samples is a bitwise prefix of a draw of S' > S samples (same seed,
+ * tag and factor); a chain's noise depends on B only through k = b T + t; B T >= 2^32 is rejected (k is a 32-bit word).
+ *
+ * L (TRI), G (FULL), y (VEC): packed arrays of a lane-per-segment plan (d <= 8); x [S, B, T, d] natural, device.  scratch: at least
+ * mfgm_packed_sample_scratch_doubles(plan, S) doubles of the caller's (the plan workspace is not touched: its coarse-level factors
+ * belong to the latest factorisation).  Returns 1 for a wide plan, n_samples < 0, a missing L, G, y, x or scratch when n_samples > 0,
+ * B T >= 2^32, or more than 65535 sample groups (csrc/mfgm_sample.h, sample_k); n_samples = 0 is a no-op. */
+size_t mfgm_packed_sample_scratch_doubles(const mfgm_plan* plan, int n_samples);
+int mfgm_packed_sample(const mfgm_plan* plan, const double* L, const double* G, const double* y, int n_samples,
+                       unsigned long long seed, unsigned int stream_tag, double* x /* [S, B, T, d] natural */,
+                       double* scratch, void* stream);
 
 #ifdef __cplusplus
 }

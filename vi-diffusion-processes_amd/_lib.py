@@ -137,6 +137,8 @@ EXPORTS = {
     "mfgm_normal_fill": (ctypes.c_int, [ctypes.c_ulonglong, ctypes.c_uint] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2),
     "mfgm_euler_maruyama": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3
                             + [ctypes.c_ulonglong] + [ctypes.c_void_p] * 2),
+    "mfgm_packed_sample_scratch_doubles": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int]),
+    "mfgm_packed_sample": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_uint] + [ctypes.c_void_p] * 3),
 }
 
 

@@ -39,6 +39,14 @@ class MultivariateGaussian:
         self.ve_constant = -float(self.log_det_chol) - 0.5 * self.obs_dim * math.log(2.0 * math.pi)
         self._g_cache = None
 
+    def predict_mean_and_var(self, f_means, f_covariances):
+        """Marginals of y (multivariate_gaussian.py:117-136): (f_means, f_covariances + L L^T), or with marginal variances
+        ([..., n, d]) the diagonal of L L^T added."""
+        cov = self._chol @ self._chol.T
+        if f_covariances.dim() == f_means.dim():
+            return f_means, f_covariances + torch.diagonal(cov)
+        return f_means, f_covariances + cov
+
     def variational_expectations(self, f_means, f_covariances, observations):
         """-1/2 tr(S^{-1} S_i) + log N(y_i; mu_i, S) (multivariate_gaussian.py:80-115); shape [..., n]."""
         Sinv = self.inv_covariance
@@ -71,6 +79,10 @@ class Gaussian:
 
     def __init__(self, variance):
         self.variance = float(variance)
+
+    def predict_mean_and_var(self, f_means, f_vars):
+        """(f_means, f_vars + variance) (gpflow.likelihoods.Gaussian)."""
+        return f_means, f_vars + self.variance
 
     def variational_expectations(self, f_means, f_vars, observations):
         v = self.variance

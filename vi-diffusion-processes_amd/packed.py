@@ -169,6 +169,12 @@ class Plan:
                                                     _ptr(self.ws), _stream()), "mfgm_packed_selinv_form")
         return dict(Sig=Sig, Sub=Sub, x=x)
 
+    def sample(self, f, n_samples, seed, stream=1):
+        """Seeded draws x = L^{-T} (y + eps) [S, B, T, d] from the form-0 factor dict `f` of `factor` (include/mfgm.h,
+        mfgm_packed_sample; eps from the normal stream with tag `stream`).  d > 8 takes the natural-layout route (sampling.py)."""
+        from . import sampling
+        return sampling.sample(self, f, n_samples, seed, stream)
+
     # -- local kernels --------------------------------------------------------------------------
     def lincomb(self, out, a, x, b=0.0, y=None, c=0.0, z=None):
         """out = a*x + b*y + c*z on flat packed arrays (in place allowed)."""

@@ -186,12 +186,21 @@ class StateSpaceModel:
         return self._unflat(kl)
 
 
-def _ssm_sample(self, sample_shape, generator=None):
+def _ssm_sample(self, sample_shape, generator=None, *, seed=None, stream=1):
     """
     Sample trajectories (state_space_model.py:298-324): x = (A^{-1})^{-1} (m + chol eps), i.e. a solve against the unit
     lower block-bidiagonal A^{-1} (partitioned on the device).  Returns sample_shape + batch_shape + [T, d].
+    With a `seed` the draw follows the sampling contract of include/mfgm.h instead: x = L^{-T} (y + eps) from the factor of the
+    precision this model already holds (`_posterior_packed`), eps from the normal stream with tag `stream`.
     """
     from .block_tri_diag import LowerTriangularBlockTriDiagonal
+    if seed is not None:
+        if generator is not None:
+            raise ValueError("sample: give either a seed or a torch generator, not both")
+        from .sampling import sample_shape_tuple
+        sample_shape, S = sample_shape_tuple(sample_shape)
+        x = self.plan.sample(self._posterior_packed()["f"], S, seed, stream)
+        return x.reshape(sample_shape + self.batch_shape + (self.T, self.d))
     if isinstance(sample_shape, int):
         sample_shape = (sample_shape,)
     sample_shape = tuple(sample_shape)

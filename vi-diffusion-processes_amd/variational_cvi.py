@@ -37,6 +37,16 @@ class GaussianProcessRegression:
         if chol_obs_covariance is None:
             chol_obs_covariance = torch.zeros((1, 1), dtype=torch.float64, device=self._observations.device)
         self._chol_obs_covariance = chol_obs_covariance
+        self._mean_function = mean_function
+
+    @property
+    def posterior(self):
+        """gaussian_process_regression.py:136-150: the Kalman posterior as an AnalyticPosteriorProcess with a MultivariateGaussian of
+        the observation noise."""
+        from .likelihoods import MultivariateGaussian
+        from .posterior import AnalyticPosteriorProcess
+        return AnalyticPosteriorProcess(self.posterior_state_space_model, self._kernel, self._time_points,
+                                        MultivariateGaussian(self._chol_obs_covariance), self._mean_function)
 
     @property
     def _kalman(self):
@@ -116,6 +126,12 @@ class GaussianProcessWithSitesBase:
         q = naturals_to_ssm_params_packed(pl, lin, diag, sub)
         q.batch_shape = self.dist_p.batch_shape
         return q
+
+    @property
+    def posterior(self):
+        """variational_cvi.py:146-153: the posterior process on dist_q."""
+        from .posterior import ConditionalProcess
+        return ConditionalProcess(self.dist_q, self._kernel, self._time_points, getattr(self, "_mean_function", None))
 
     @property
     def posterior_kalman(self):
