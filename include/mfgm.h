@@ -763,6 +763,24 @@ int mfgm_packed_sample(const mfgm_plan* plan, const double* L, const double* G, 
                        unsigned long long seed, unsigned int stream_tag, double* x /* [S, B, T, d] natural */,
                        double* scratch, void* stream);
 
+/* ---- scalar non-Gaussian likelihoods of the CVI models (Bernoulli-probit, Poisson-exp) -----------------------------------------------
+ * Contract (fp64), per observation i with q(f_i) = N(mu, v), sigma = sqrt(v), y = y_i; the 20-point rule of gpflow's NDiagGHQuadrature:
+ *      (xi_k, w_k) = numpy.polynomial.hermite.hermgauss(20),  W_k = w_k / sqrt(pi),  X_k = mu + sqrt(2) sigma xi_k,
+ *      VE = sum_k W_k l(X_k),   dVE/dmu = sum_k W_k l'(X_k),   dVE/dv = sum_k W_k l'(X_k) xi_k / (sqrt(2) sigma)
+ * (the derivatives of the RULE, as a tape over it gives them, not 1/2 E[l'']).  Site gradients (expectation parameters):
+ *      g1 = dVE/dmu - 2 (dVE/dv) mu,   g2 = dVE/dv.
+ *   kind MFGM_LIK_BERNOULLI, param = jitter j in [0, 1/2):  Phi(x) = erfc(-x / sqrt 2) / 2,  s = +1 if y == 1 else -1 (any y other than 1
+ *      counts as 0),  l(f) = log(j + (1 - 2j) Phi(s f)),  l'(f) = s (1 - 2j) phi(f) / (j + (1 - 2j) Phi(s f)).
+ *   kind MFGM_LIK_POISSON, param = bin size b > 0, closed form:  m = b exp(mu + v / 2),
+ *      VE = y log b + y mu - m - lgamma(y + 1),  dVE/dmu = y - m,  dVE/dv = -m / 2.
+ * v <= 0 is undefined (NaN, not clamped).  fmu, fvar, y [n] and the outputs ve, g1, g2 [n] are device arrays; a null output is not
+ * written.  One lane per observation; no host synchronisation, no allocation (graph-capturable).  Returns 1 for an unknown kind, a
+ * param out of range, or a missing input when n > 0; n = 0 is a no-op. */
+#define MFGM_LIK_BERNOULLI 1
+#define MFGM_LIK_POISSON 2
+int mfgm_scalar_lik(int kind, size_t n, const double* fmu, const double* fvar, const double* y, double param, double* ve, double* g1,
+                    double* g2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

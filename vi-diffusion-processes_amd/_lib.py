@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFGM_LIB") or os.path.join(_HERE, "csrc", "libmfgm.so")
 
 VEC, FULL, SYM, TRI = 0, 1, 2, 3
+# mfgm_scalar_lik kinds (include/mfgm.h)
+LIK_BERNOULLI, LIK_POISSON = 1, 2
 
 _lib = None
 
@@ -139,6 +141,7 @@ EXPORTS = {
                             + [ctypes.c_ulonglong] + [ctypes.c_void_p] * 2),
     "mfgm_packed_sample_scratch_doubles": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int]),
     "mfgm_packed_sample": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_uint] + [ctypes.c_void_p] * 3),
+    "mfgm_scalar_lik": (ctypes.c_int, [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 4),
 }
 
 

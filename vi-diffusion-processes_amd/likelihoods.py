@@ -4,6 +4,9 @@ gpflow.likelihoods.Gaussian for the scalar CVI-GP case): variational expectation
 closed form (the reference differentiates them with a GradientTape, variational_cvi_sde.py:204-220).
 Observation counts are tiny next to the time grid (n_obs << T), so these run as small batched torch ops on
 the gathered observation nodes.
+
+The scalar non-Gaussian likelihoods of the CVI models (Bernoulli, Poisson; gpflow.likelihoods) follow at the end: 20-point
+Gauss-Hermite variational expectations and their site gradients, natively in one launch (mfgm_scalar_lik).
 """
 import math
 import weakref
@@ -108,3 +111,167 @@ class Gaussian:
             c = self._g_cache = (weakref.ref(observations), observations._version, tuple(f_vars.shape), v, observations / v,
                                  torch.full_like(f_vars, -0.5 / v))
         return c[4], c[5]
+
+
+# ---- scalar non-Gaussian likelihoods (gpflow.likelihoods.Bernoulli / Poisson, the ones the reference's CVI walkthroughs fit) ----------
+class ScalarQuadratureLikelihood:
+    """A scalar likelihood p(y | f) given by its log density `log_prob(F, Y)` (a torch function, broadcasting), with the variational
+    expectations taken by the n_gh-point Gauss-Hermite rule of gpflow's NDiagGHQuadrature (include/mfgm.h, mfgm_scalar_lik):
+        X_k = mu + sqrt(2) sigma xi_k,   VE = sum_k W_k log_prob(X_k, y),   W_k = w_k / sqrt(pi)
+    and the site gradients by autograd through that rule -- what the reference's GradientTape over
+    likelihood.variational_expectations gives (variational_cvi.py:332-349).  The generic route: torch only.  Shapes as Gaussian:
+    f_means, f_vars, observations [..., n, 1]; variational_expectations [..., n]; (g1, g2) [..., n, 1].  v <= 0 is not clamped.
+
+    Subclasses with a `kind` (Bernoulli, Poisson) run the same quantities in one HIP launch (mfgm_scalar_lik) when the tensors are on
+    the device, contiguous fp64, and nothing asks for a gradient; otherwise they take this torch route, which stays differentiable
+    (classic_elbo_tape, ssm_natgrad).  The gradients depend on q: nothing is cached across calls."""
+
+    kind = None          # mfgm_scalar_lik kind of the native route; None: torch only
+
+    def __init__(self, log_prob, n_gh=20):
+        import numpy as np
+        self.log_prob = log_prob
+        self.n_gh = int(n_gh)
+        xi, w = np.polynomial.hermite.hermgauss(self.n_gh)
+        self._xi, self._w = xi, w / math.sqrt(math.pi)
+        self._rule_cache = {}
+
+    @property
+    def param(self):
+        """The scalar parameter handed to mfgm_scalar_lik (jitter / bin size)."""
+        raise NotImplementedError
+
+    def _rule(self, like):
+        """(xi, W) as tensors on `like`'s device: constants of the rule (not of q), made once per device."""
+        key = str(like.device)
+        r = self._rule_cache.get(key)
+        if r is None:
+            r = self._rule_cache[key] = (torch.tensor(self._xi, dtype=torch.float64, device=like.device),
+                                         torch.tensor(self._w, dtype=torch.float64, device=like.device))
+        return r
+
+    def _nodes(self, f_means, f_vars):
+        xi, w = self._rule(f_means)
+        return f_means[..., None] + math.sqrt(2.0) * torch.sqrt(f_vars)[..., None] * xi, w
+
+    def _ve_torch(self, f_means, f_vars, observations):
+        """[..., n, 1]: sum_k W_k log_prob(X_k, y) (differentiable)."""
+        X, w = self._nodes(f_means, f_vars)
+        return (self.log_prob(X, observations[..., None]) * w).sum(-1)
+
+    # ---- native route ----------------------------------------------------------------------------------------------------------------
+    def _native(self, f_means, f_vars, observations):
+        if self.kind is None or not f_means.is_cuda:
+            return False
+        ts = (f_means, f_vars, observations)
+        if any(t.requires_grad for t in ts) and torch.is_grad_enabled():
+            return False
+        return all(t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.shape == f_means.shape for t in ts)
+
+    def _launch(self, f_means, f_vars, observations, ve=False, grads=False):
+        from . import _lib
+        from .packed import _ptr, _stream
+        n = f_means.numel()
+        mk = lambda: torch.empty(f_means.shape, dtype=torch.float64, device=f_means.device)
+        out_ve = mk() if ve else None
+        g1, g2 = (mk(), mk()) if grads else (None, None)
+        _lib.check(_lib.load().mfgm_scalar_lik(self.kind, n, _ptr(f_means), _ptr(f_vars), _ptr(observations), float(self.param),
+                                               _ptr(out_ve), _ptr(g1), _ptr(g2), _stream()), "mfgm_scalar_lik")
+        return out_ve, g1, g2
+
+    # ---- interface of the CVI models -----------------------------------------------------------------------------------------------
+    def variational_expectations(self, f_means, f_vars, observations):
+        """E_q log p(y_i | f_i), [..., n]."""
+        if self._native(f_means, f_vars, observations):
+            return self._launch(f_means, f_vars, observations, ve=True)[0].sum(-1)
+        return self._ve_torch(f_means, f_vars, observations).sum(-1)
+
+    def variational_expectations_sum(self, f_means, f_vars, observations):
+        """Sum of variational_expectations over every point, a device scalar (no host synchronisation)."""
+        return self.variational_expectations(f_means, f_vars, observations).sum()
+
+    def ve_gradients_expectation(self, f_means, f_vars, observations):
+        """(g1, g2) = (dVE/dmu - 2 (dVE/dv) mu, dVE/dv), [..., n, 1] each: the gradient of sum_i VE_i with respect to the expectation
+        parameters (mu, v + mu^2) (gradient_transformation_mean_var_to_expectation, variational_cvi.py:448-462)."""
+        if self._native(f_means, f_vars, observations):
+            _, g1, g2 = self._launch(f_means, f_vars, observations, grads=True)
+            return g1, g2
+        with torch.enable_grad():
+            mu = f_means.detach().requires_grad_(True)
+            v = f_vars.detach().requires_grad_(True)
+            dmu, dv = torch.autograd.grad(self._ve_torch(mu, v, observations.detach()).sum(), [mu, v])
+        return dmu - 2.0 * dv * f_means.detach(), dv
+
+    def predict_log_density(self, f_means, f_vars, observations):
+        """log int p(y | f) q(f) df by the rule in log space (gpflow's quadrature.logspace): logsumexp_k(log W_k + log_prob(X_k, y)),
+        [..., n]."""
+        X, w = self._nodes(f_means, f_vars)
+        return torch.logsumexp(self.log_prob(X, observations[..., None]) + torch.log(w), dim=-1).sum(-1)
+
+    def predict_mean_and_var(self, f_means, f_vars):
+        raise NotImplementedError("a likelihood given by its log density alone has no closed-form predictive moments")
+
+
+def _probit(x):
+    """Phi(x) = erfc(-x / sqrt 2) / 2 (accurate in the lower tail, where 1/2 (1 + erf) is not)."""
+    return 0.5 * torch.erfc(-x * (1.0 / math.sqrt(2.0)))
+
+
+class Bernoulli(ScalarQuadratureLikelihood):
+    """gpflow.likelihoods.Bernoulli with its default probit link and jitter j = 1e-3:  p_j(f) = j + (1 - 2j) Phi(f);  log p(y | f) =
+    log p_j(f) for y == 1 and log(1 - p_j(f)) for any other y (gpflow's where(y == 1, p, 1 - p)), with 1 - p_j(f) computed as
+    j + (1 - 2j) Phi(-f).  Variational expectations by the 20-point rule; natively on the device (mfgm_scalar_lik kind 1)."""
+
+    kind = 1
+
+    def __init__(self, jitter=1e-3):
+        self.jitter = float(jitter)
+        super().__init__(self._log_prob, n_gh=20)
+
+    @property
+    def param(self):
+        return self.jitter
+
+    def _p(self, f):
+        return self.jitter + (1.0 - 2.0 * self.jitter) * _probit(f)
+
+    def _log_prob(self, F, Y):
+        return torch.log(self._p(torch.where(Y == 1, F, -F)))
+
+    def predict_mean_and_var(self, f_means, f_vars):
+        """p = p_j(mu / sqrt(1 + v)) and p - p^2 (closed form, gpflow.likelihoods.Bernoulli)."""
+        p = self._p(f_means / torch.sqrt(1.0 + f_vars))
+        return p, p - p * p
+
+    def predict_log_density(self, f_means, f_vars, observations):
+        """log Bernoulli(y; p), p = p_j(mu / sqrt(1 + v)) (closed form), 1 - p in the Phi(-x) form; [..., n]."""
+        x = f_means / torch.sqrt(1.0 + f_vars)
+        return torch.log(self._p(torch.where(observations == 1, x, -x))).sum(-1)
+
+
+class Poisson(ScalarQuadratureLikelihood):
+    """gpflow.likelihoods.Poisson with the exp link and bin size b:  log p(y | f) = y log(b e^f) - b e^f - lgamma(y + 1).  Variational
+    expectations in closed form (as gpflow): VE = y log b + y mu - b e^{mu + v/2} - lgamma(y + 1); natively on the device
+    (mfgm_scalar_lik kind 2)."""
+
+    kind = 2
+
+    def __init__(self, binsize=1.0):
+        self.binsize = float(binsize)
+        super().__init__(self._log_prob, n_gh=20)
+
+    @property
+    def param(self):
+        return self.binsize
+
+    def _log_prob(self, F, Y):
+        return Y * (math.log(self.binsize) + F) - self.binsize * torch.exp(F) - torch.lgamma(Y + 1.0)
+
+    def _ve_torch(self, f_means, f_vars, observations):
+        y = observations
+        return y * math.log(self.binsize) + y * f_means - self.binsize * torch.exp(f_means + 0.5 * f_vars) - torch.lgamma(y + 1.0)
+
+    def predict_mean_and_var(self, f_means, f_vars):
+        """Exact moments of y: m = b e^{mu + v/2}, m + (e^v - 1) m^2 (gpflow takes them by quadrature)."""
+        m = self.binsize * torch.exp(f_means + 0.5 * f_vars)
+        return m, m + torch.expm1(f_vars) * m * m

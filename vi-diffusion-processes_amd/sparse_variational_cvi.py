@@ -476,3 +476,9 @@ class SparseCVIGaussianProcess:
 
     def loss(self, input_data):
         return -self.classic_elbo(input_data)
+
+    def predict_log_density(self, input_data, full_output_cov=False):
+        """log p(y* | data) per point (markovflow/models/models.py:206-227): the likelihood's predict_log_density of posterior.predict_f."""
+        X, Y = input_data
+        f_mean, f_var = self.posterior.predict_f(X, full_output_cov=full_output_cov)
+        return self._likelihood.predict_log_density(f_mean, f_var, Y)

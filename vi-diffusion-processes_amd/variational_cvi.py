@@ -322,6 +322,12 @@ class CVIGaussianProcess(GaussianProcessWithSitesBase):
         step.graph = graph
         return step
 
+    def predict_log_density(self, input_data, full_output_cov=False):
+        """log p(y* | data) per point (variational_cvi.py:406-421): the likelihood's predict_log_density of posterior.predict_f."""
+        X, Y = input_data
+        f_mean, f_var = self.posterior.predict_f(X, full_output_cov=full_output_cov)
+        return self._likelihood.predict_log_density(f_mean, f_var, Y)
+
     def classic_elbo(self):
         """sum_i E_q log p(y_i | f_i) - KL[q(s) || p(s)] (variational_cvi.py:381-404)."""
         fx_mus, fx_covs = self.predict_f_at_data()
