@@ -514,6 +514,41 @@ typedef struct mfgm_kernel_spec {
 int mfgm_packed_stationary_ssm(const mfgm_plan* plan, const mfgm_kernel_spec* spec, const double* time_deltas, double* A,
                                double* off, double* chol, int* info, void* stream);
 
+/* Factor kinds of mfgm_kernel_terms.  MATERN12 also holds Ornstein-Uhlenbeck (rate = decay, var = diffusion / (2 decay));
+ * rate = sqrt(3)/l for MATERN32, sqrt(5)/l for MATERN52, omega = 2 pi / period for HARMONIC (kernels/periodic.py:27-203), unused
+ * for CONSTANT (kernels/constant.py:28-153).  State dimensions 1, 2, 3, 1, 2. */
+#define MFGM_FACTOR_MATERN12 1
+#define MFGM_FACTOR_MATERN32 2
+#define MFGM_FACTOR_MATERN52 3
+#define MFGM_FACTOR_CONSTANT 4
+#define MFGM_FACTOR_HARMONIC 5
+
+/* A sum of up to 8 terms (Sum / ConcatKernel, kernels/sde_kernel.py:540-687), each the product of up to 3 factors (Product,
+ * sde_kernel.py:691-826): term c occupies the state indices offset[c] .. offset[c] + prod_f dim(kind[c][f]) - 1, its A, Pinf and
+ * H are the Kronecker products of its factors' (factor 0 outermost).  Total state dimension d <= 8. */
+typedef struct mfgm_kernel_terms {
+    int nterm;
+    int nfactor[8];
+    int offset[8];
+    int kind[8][3];
+    double rate[8][3];
+    double var[8][3];
+    double mean[8];
+    double jitter;
+} mfgm_kernel_terms;
+
+/* Kernel terms -> packed SSM parameters on a time grid (SDEKernel.state_space_model, sde_kernel.py:153-171), the layout and
+ * outputs of mfgm_packed_stationary_ssm.  Per term, with P_f the factor's Pinf and M_f = A_f P_f A_f^T (M_f = P_f exactly for
+ * CONSTANT and HARMONIC, whose process noise is zero: constant.py:94-113, periodic.py:134-150):
+ *   Q_term = (P_g - M_g) (x) (x)_{f != g} P_f   when g is the only factor with M_f != P_f,
+ *            0                                 when there is none,
+ *            (x)_f P_f - (x)_f M_f             otherwise  (StationaryKernel.transition_statistics, sde_kernel.py:421-446),
+ * Q = blockdiag(Q_term) + jitter I, Cholesky factored (an exactly-zero Q stays zero; a Q neither positive definite nor zero sets
+ * *info), b = (I - A) m; node 0 holds (m, chol(Pinf + jitter I)).  A Matern-only tree gives what mfgm_packed_stationary_ssm
+ * gives.  Returns 1 for d > 8, bad term / factor counts or kinds, offsets that do not tile 0 .. d-1, or d != the plan's d. */
+int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_terms* terms, const double* time_deltas, double* A,
+                           double* off, double* chol, int* info, void* stream);
+
 /* VDP (markovflow/models/vi_sde.py `VariationalMarkovGP`): drift f_i(x) = af_i x - bf_i x^3, diagonal diffusion q,
  * q(x0) = N(mu0, chol0 chol0^T) (packed lower triangle), grid step dt, learning rate lr. */
 typedef struct mfgm_vdp_params {

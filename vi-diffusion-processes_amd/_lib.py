@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFGM_LIB") or os.path.join(_HERE, "csrc", "libmfgm.so")
 
 VEC, FULL, SYM, TRI = 0, 1, 2, 3
+# mfgm_kernel_terms factor kinds (include/mfgm.h)
+FACTOR_MATERN12, FACTOR_MATERN32, FACTOR_MATERN52, FACTOR_CONSTANT, FACTOR_HARMONIC = 1, 2, 3, 4, 5
 # mfgm_scalar_lik kinds (include/mfgm.h)
 LIK_BERNOULLI, LIK_POISSON = 1, 2
 
@@ -60,6 +62,7 @@ EXPORTS = {
     "mfgm_packed_sde_kl": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 14),
     "mfgm_packed_linearize_cubic": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_stationary_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
+    "mfgm_packed_kernel_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_vdp_workspace_doubles": (ctypes.c_size_t, [ctypes.c_void_p]),
     "mfgm_packed_vdp_to_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_vdp_to_naturals": (ctypes.c_int, [ctypes.c_void_p] * 10),
@@ -188,6 +191,13 @@ class KernelSpec(ctypes.Structure):
     """mfgm_kernel_spec (include/mfgm.h)."""
     _fields_ = [("ncomp", ctypes.c_int), ("order", ctypes.c_int * 8), ("offset", ctypes.c_int * 8), ("lam", ctypes.c_double * 8),
                 ("var", ctypes.c_double * 8), ("mean", ctypes.c_double * 8), ("jitter", ctypes.c_double)]
+
+
+class KernelTerms(ctypes.Structure):
+    """mfgm_kernel_terms (include/mfgm.h)."""
+    _fields_ = [("nterm", ctypes.c_int), ("nfactor", ctypes.c_int * 8), ("offset", ctypes.c_int * 8), ("kind", (ctypes.c_int * 3) * 8),
+                ("rate", (ctypes.c_double * 3) * 8), ("var", (ctypes.c_double * 3) * 8), ("mean", ctypes.c_double * 8),
+                ("jitter", ctypes.c_double)]
 
 
 class VdpParams(ctypes.Structure):

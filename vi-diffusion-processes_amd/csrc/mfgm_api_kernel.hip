@@ -1,0 +1,79 @@
+// Sums of products of stationary SDE kernels -> packed SSM parameters (mfgm_kernel_ssm.h).
+#include "mfgm_internal.h"
+#include "mfgm_kernel_ssm.h"
+
+using namespace mfgm;
+
+namespace {
+int factor_dim(int kind) {
+    switch (kind) {
+        case MFGM_FACTOR_MATERN12: case MFGM_FACTOR_CONSTANT: return 1;
+        case MFGM_FACTOR_MATERN32: case MFGM_FACTOR_HARMONIC: return 2;
+        case MFGM_FACTOR_MATERN52: return 3;
+        default: return 0;
+    }
+}
+
+template <int D>
+int kernel_ssm_impl(const Plan& P, const KernelTermsDev& kt, const double* dts, double* A, double* off, double* chol, int* info,
+                    hipStream_t st) {
+    const LevelDesc& lv = P.lv[0];
+    hipLaunchKernelGGL((k_kernel_ssm<D>), dim3(lv.Lpad / 64), dim3(64), 0, st, lv, kt, dts, A, off, chol, info);
+    MFGM_CHECK_LAUNCH();
+    return 0;
+}
+}  // namespace
+
+extern "C" int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_terms* terms, const double* time_deltas, double* A,
+                                      double* off, double* chol, int* info, void* stream) {
+    if (!plan || !terms || !A || !off || !chol || !info) return 1;
+    const Plan& P = plan->p;
+    if (P.wide || P.d > 8) return 1;
+    if (P.T > 1 && !time_deltas) return 1;
+    const mfgm_kernel_terms& in = *terms;
+    if (in.nterm < 1 || in.nterm > 8) return 1;
+    KernelTermsDev kt;
+    memset(&kt, 0, sizeof(kt));
+    kt.nterm = in.nterm;
+    int dim = 0;
+    for (int c = 0; c < in.nterm; ++c) {
+        const int nf = in.nfactor[c];
+        if (nf < 1 || nf > 3 || in.offset[c] != dim) return 1;
+        int n = 1;
+        for (int f = 0; f < nf; ++f) {
+            const int fd = factor_dim(in.kind[c][f]);
+            if (fd == 0) return 1;
+            n *= fd;
+        }
+        if (dim + n > 8) return 1;
+        // 1 x 1 factors commute through the Kronecker product: move them behind the others, keeping the others' order
+        int slot = 0, shape = 0;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int f = 0; f < nf; ++f) {
+                const int fd = factor_dim(in.kind[c][f]);
+                if ((fd > 1) != (pass == 0)) continue;
+                kt.kind[c][slot] = in.kind[c][f];
+                kt.rate[c][slot] = in.rate[c][f];
+                kt.var[c][slot] = in.var[c][f];
+                if (fd > 1) shape = shape * 10 + fd;
+                ++slot;
+            }
+        switch (shape) {
+            case 0: kt.shape[c] = KT_SHAPE_1; break;
+            case 2: kt.shape[c] = KT_SHAPE_2; break;
+            case 3: kt.shape[c] = KT_SHAPE_3; break;
+            case 22: kt.shape[c] = KT_SHAPE_22; break;
+            case 23: kt.shape[c] = KT_SHAPE_23; break;
+            case 32: kt.shape[c] = KT_SHAPE_32; break;
+            case 222: kt.shape[c] = KT_SHAPE_222; break;
+            default: return 1;
+        }
+        kt.offset[c] = dim;
+        dim += n;
+    }
+    if (dim != P.d) return 1;
+    for (int i = 0; i < dim; ++i) kt.mean[i] = in.mean[i];
+    kt.jitter = in.jitter;
+    hipStream_t st = (hipStream_t)stream;
+    MFGM_DISPATCH_D(P.d, (kernel_ssm_impl<DD>(P, kt, time_deltas, A, off, chol, info, st)));
+}

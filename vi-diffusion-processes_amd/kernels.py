@@ -3,6 +3,10 @@ Host-side mirror of the stationary SDE kernels on the path (markovflow/kernels/m
 `OrnsteinUhlenbeck`, `Matern32`, `Matern52`; markovflow/kernels/sde_kernel.py: `StationaryKernel`, `Sum`).
 `state_space_model(time_points)` evaluates the closed-form matrix exponentials, the process covariances and their
 Cholesky factors in one HIP kernel (k_stationary_ssm) directly in the packed layout.
+
+Seasonal priors (markovflow/kernels/periodic.py `HarmonicOscillator`, kernels/constant.py `Constant`, kernels/sde_kernel.py
+`Product`) and any Sum / Product tree holding them go through the generic term kernel k_kernel_ssm (mfgm_packed_kernel_ssm) for
+state_dim <= 8 and through the torch closed forms otherwise.
 """
 import math
 
@@ -233,6 +237,108 @@ class StationaryKernel:
             off += order
         return EmissionModel(h.expand(tuple(time_points.shape) + (1, self.state_dim)).contiguous(), constant_matrix=h)
 
+    # -- the generic (term-tree) route: every kernel, primitive or combined, as parts of the exact-Q rule ------------------------------
+    _matern_tree = True      # only Matern / OU leaves and Sums of them: the k_stationary_ssm route above
+
+    def _parts(self, dt, leaves=None):
+        """(A [..., d, d], Pinf [d, d], Qterm [..., d, d], exact) at the time gaps dt [...]: Qterm = Pinf - A Pinf A^T without jitter
+        (exactly zero when `exact`).  leaves: hyperparameter_leaves() to differentiate through, or None for the current values."""
+        comps = self._components() if leaves is None else self._components_t(leaves)
+        (order, lam, var), = comps
+        lam = torch.as_tensor(lam, dtype=torch.float64, device=dt.device)
+        var = torch.as_tensor(var, dtype=torch.float64, device=dt.device)
+        t = dt[..., None, None]
+        ex = torch.exp(-lam * t)
+        eye = torch.eye(order, dtype=torch.float64, device=dt.device)
+        one, zero = torch.ones_like(lam), torch.zeros_like(lam)
+        if order == 1:
+            A, P = ex * eye, var.reshape(1, 1)
+        elif order == 2:
+            N = torch.stack([torch.stack([lam, one]), torch.stack([-lam ** 2, -lam])])
+            A = ex * (eye + N * t)
+            P = var * torch.stack([torch.stack([one, zero]), torch.stack([zero, lam ** 2])])
+        else:
+            N = torch.stack([torch.stack([lam, one, zero]), torch.stack([zero, lam, one]),
+                             torch.stack([-lam ** 3, -3.0 * lam ** 2, -2.0 * lam])])
+            A = ex * (eye + N * t + (N @ N) * (0.5 * t * t))
+            l23 = lam ** 2 / 3.0
+            P = var * torch.stack([torch.stack([one, zero, -l23]), torch.stack([zero, l23, zero]), torch.stack([-l23, zero, lam ** 4])])
+        return A, P, P - A @ P @ A.transpose(-1, -2), False
+
+    def _emission_row(self):
+        """H of this kernel as a [state_dim] vector."""
+        h = torch.zeros(self.state_dim, dtype=torch.float64)
+        h[0] = 1.0
+        return h
+
+    def _terms(self):
+        """This kernel as mfgm_kernel_terms rows: [[(kind, rate, var), ...] per term], or None where the struct cannot express it."""
+        (order, lam, var), = self._components()
+        return [[(order, float(lam), float(var))]]
+
+    def _generic_ssm(self, time_points, plan=None):
+        t, bs = _flat(time_points, 1)
+        B, T = t.shape
+        if plan is None:
+            plan = Plan(B, T, self.state_dim, device=t.device)
+        dts = (t[:, 1:] - t[:, :-1]).contiguous()
+        terms = self._terms() if self.state_dim <= 8 else None
+        if terms is None or len(terms) > 8:
+            try:
+                return self._state_space_model_wide(dts, bs, plan)
+            except ArithmeticError as e:
+                raise ArithmeticError(_NOT_PD) from e
+        A, off_, chol = plan.kernel_ssm(self._terms_struct(terms), dts)
+        try:
+            plan.check_info()
+        except ArithmeticError as e:
+            raise ArithmeticError(_NOT_PD) from e
+        ssm = _ssm_from_packed(plan, A, off_, chol)
+        ssm.batch_shape = bs
+        return ssm
+
+    def _terms_struct(self, terms=None):
+        """mfgm_kernel_terms of this kernel (any tree _terms() expresses, Matern-only ones included)."""
+        terms = self._terms() if terms is None else terms
+        if terms is None or len(terms) > 8 or self.state_dim > 8:
+            raise ValueError("the term kernel takes up to 8 terms of up to 3 primitive factors and state_dim <= 8")
+        kt = _lib.KernelTerms()
+        kt.nterm = len(terms)
+        off = 0
+        for c, factors in enumerate(terms):
+            kt.nfactor[c], kt.offset[c] = len(factors), off
+            n = 1
+            for f, (kind, rate, var) in enumerate(factors):
+                kt.kind[c][f], kt.rate[c][f], kt.var[c][f] = kind, rate, var
+                n *= _FACTOR_DIM[kind]
+            off += n
+        m = self.state_mean
+        for i in range(self.state_dim):
+            kt.mean[i] = float(m[i])
+        kt.jitter = self.jitter
+        return kt
+
+    def _generic_local(self, time_deltas):
+        A, _, Qt, _ = self._parts(time_deltas)
+        d = self.state_dim
+        return A, Qt + self.jitter * torch.eye(d, dtype=A.dtype, device=A.device)
+
+    def _generic_differentiable_ssm(self, time_points, leaves=None, plan=None):
+        from . import tape
+        t = time_points.reshape(-1)
+        dev = t.device
+        if leaves is None:
+            leaves = self.hyperparameter_leaves(dev)
+        A, Pinf, Qt, exact = self._parts(t[1:] - t[:-1], leaves)
+        d = self.state_dim
+        jit = self.jitter * torch.eye(d, dtype=torch.float64, device=dev)
+        Q = Qt + jit
+        m = self.state_mean.to(dev)
+        b = m - (A @ m[:, None])[..., 0]
+        cq = torch.zeros_like(Q) if (exact and self.jitter == 0.0) else tape.cholesky(0.5 * (Q + Q.transpose(-1, -2)))
+        ssm = tape.TapeSSM(m[None], tape.cholesky(Pinf + jit)[None], A[None], b[None], cq[None], plan=plan)
+        return ssm, leaves
+
 
 def _check(lengthscale, variance):
     if lengthscale <= 0.0 or variance <= 0.0:
@@ -352,3 +458,240 @@ class Sum(StationaryKernel):
         if any(k.jitter != 0.0 for k in self.kernels):
             raise ValueError("per-component jitter inside Sum is not supported on the HIP path; set it on the Sum")
         return spec
+
+    # -- children beyond Matern / OU (HarmonicOscillator, Constant, Product): the term-tree route -------------------------------------
+    @property
+    def _matern_tree(self):
+        return all(k._matern_tree for k in self.kernels)
+
+    def _parts(self, dt, leaves=None):
+        lv = [None] * len(self.kernels) if leaves is None else leaves
+        parts = [k._parts(dt, l) for k, l in zip(self.kernels, lv)]
+        return (_block_diag_b([p[0] for p in parts]), _block_diag_b([p[1] for p in parts]), _block_diag_b([p[2] for p in parts]),
+                all(p[3] for p in parts))
+
+    def _emission_row(self):
+        return torch.cat([k._emission_row() for k in self.kernels])
+
+    def _terms(self):
+        out = []
+        for k in self.kernels:
+            t = k._terms()
+            if t is None:
+                return None
+            out.extend(t)
+        return out
+
+    @property
+    def steady_state_covariance(self):
+        if self._matern_tree:
+            return super().steady_state_covariance
+        return self._parts(torch.zeros(1, dtype=torch.float64))[1].detach()
+
+    @property
+    def feedback_matrix(self):
+        if self._matern_tree:
+            return super().feedback_matrix
+        return torch.block_diag(*[k.feedback_matrix for k in self.kernels])
+
+    def state_space_model(self, time_points, plan=None):
+        if self._matern_tree:
+            return super().state_space_model(time_points, plan)
+        if any(k.jitter != 0.0 for k in self.kernels):
+            raise ValueError("per-component jitter inside Sum is not supported on the HIP path; set it on the Sum")
+        return self._generic_ssm(time_points, plan)
+
+    def transition_statistics_local(self, time_deltas):
+        if self._matern_tree:
+            return super().transition_statistics_local(time_deltas)
+        return self._generic_local(time_deltas)
+
+    def differentiable_ssm(self, time_points, leaves=None, plan=None):
+        if self._matern_tree:
+            return super().differentiable_ssm(time_points, leaves, plan)
+        return self._generic_differentiable_ssm(time_points, leaves, plan)
+
+    def generate_emission_model(self, time_points):
+        if self._matern_tree:
+            return super().generate_emission_model(time_points)
+        return _GenericKernel.generate_emission_model(self, time_points)
+
+
+_FACTOR_DIM = {_lib.FACTOR_MATERN12: 1, _lib.FACTOR_MATERN32: 2, _lib.FACTOR_MATERN52: 3, _lib.FACTOR_CONSTANT: 1,
+               _lib.FACTOR_HARMONIC: 2}
+_NOT_PD = ("the process covariance Q of the kernel's state-space model is neither positive definite nor exactly zero "
+           "(e.g. a Sum of a Matern and a HarmonicOscillator): set a jitter on the kernel")
+
+
+def _kron(X, Y):
+    """Kronecker product of the trailing square matrices, batch dimensions broadcast."""
+    a, b = X.shape[-1], Y.shape[-1]
+    out = X[..., :, None, :, None] * Y[..., None, :, None, :]
+    return out.reshape(tuple(out.shape[:-4]) + (a * b, a * b))
+
+
+def _block_diag_b(mats):
+    """Block diagonal of [..., k, k] matrices, batch dimensions broadcast."""
+    batch = torch.broadcast_shapes(*[m.shape[:-2] for m in mats])
+    n = sum(m.shape[-1] for m in mats)
+    out = torch.zeros(batch + (n, n), dtype=mats[0].dtype, device=mats[0].device)
+    o = 0
+    for m in mats:
+        k = m.shape[-1]
+        out[..., o:o + k, o:o + k] = m
+        o += k
+    return out
+
+
+class _GenericKernel(StationaryKernel):
+    """The members the models use, on the term-tree route (HIP k_kernel_ssm for d <= 8, torch closed forms otherwise)."""
+
+    _matern_tree = False
+
+    @property
+    def steady_state_covariance(self):
+        return self._parts(torch.zeros(1, dtype=torch.float64))[1].detach()
+
+    def state_space_model(self, time_points, plan=None):
+        return self._generic_ssm(time_points, plan)
+
+    def transition_statistics_local(self, time_deltas):
+        """(A, Q) for arbitrary, unordered time gaps under the exact-Q rule, the formulas of k_kernel_ssm."""
+        return self._generic_local(time_deltas)
+
+    def differentiable_ssm(self, time_points, leaves=None, plan=None):
+        return self._generic_differentiable_ssm(time_points, leaves, plan)
+
+    def generate_emission_model(self, time_points):
+        h = self._emission_row().to(time_points.device)[None]
+        return EmissionModel(h.expand(tuple(time_points.shape) + (1, self.state_dim)).contiguous(), constant_matrix=h)
+
+
+class HarmonicOscillator(_GenericKernel):
+    """periodic.py:27-203: k(tau) = variance cos(2 pi tau / period); lambda = 2 pi / period, A = [[cos, -sin], [sin, cos]](lambda dt),
+    Pinf = variance I, H = [1, 0], Q = 0 (+ jitter)."""
+    state_dim = 2
+
+    def __init__(self, variance, period, output_dim=1, jitter=0.0):
+        super().__init__(output_dim, jitter)
+        if variance <= 0.0:
+            raise ValueError("variance must be positive.")
+        if period <= 0.0:
+            raise ValueError("period must be positive.")
+        self.variance, self.period = float(variance), float(period)
+
+    @property
+    def feedback_matrix(self):
+        lam = 2.0 * math.pi / self.period
+        return torch.tensor([[0.0, -lam], [lam, 0.0]], dtype=torch.float64)
+
+    def hyperparameter_leaves(self, device="cpu"):
+        mk = lambda v: torch.tensor(float(v), dtype=torch.float64, device=device, requires_grad=True)
+        return {"variance": mk(self.variance), "period": mk(self.period)}
+
+    def _parts(self, dt, leaves=None):
+        var = torch.as_tensor(self.variance if leaves is None else leaves["variance"], dtype=torch.float64, device=dt.device)
+        period = torch.as_tensor(self.period if leaves is None else leaves["period"], dtype=torch.float64, device=dt.device)
+        x = (2.0 * math.pi / period) * dt[..., None, None]
+        c, s = torch.cos(x), torch.sin(x)
+        A = torch.cat([torch.cat([c, -s], dim=-1), torch.cat([s, c], dim=-1)], dim=-2)
+        P = var * torch.eye(2, dtype=torch.float64, device=dt.device)
+        return A, P, torch.zeros_like(A), True
+
+    def _terms(self):
+        return [[(_lib.FACTOR_HARMONIC, 2.0 * math.pi / self.period, self.variance)]]
+
+
+class Constant(_GenericKernel):
+    """constant.py:28-153: k(tau) = variance; A = [[1]], Pinf = [[variance]], H = [1], Q = 0 (+ jitter).  feedback_matrix is zero, as in
+    the reference code (its docstring says [[1]])."""
+    state_dim = 1
+
+    def __init__(self, variance, output_dim=1, jitter=0.0):
+        super().__init__(output_dim, jitter)
+        if variance <= 0:
+            raise ValueError("variance must be positive.")
+        self.variance = float(variance)
+
+    @property
+    def feedback_matrix(self):
+        return torch.zeros((1, 1), dtype=torch.float64)
+
+    def hyperparameter_leaves(self, device="cpu"):
+        return {"variance": torch.tensor(self.variance, dtype=torch.float64, device=device, requires_grad=True)}
+
+    def _parts(self, dt, leaves=None):
+        var = torch.as_tensor(self.variance if leaves is None else leaves["variance"], dtype=torch.float64, device=dt.device)
+        A = torch.ones(tuple(dt.shape) + (1, 1), dtype=torch.float64, device=dt.device)
+        return A, var.reshape(1, 1), torch.zeros_like(A), True
+
+    def _terms(self):
+        return [[(_lib.FACTOR_CONSTANT, 0.0, self.variance)]]
+
+
+class Product(_GenericKernel):
+    """sde_kernel.py:691-826: A = (x) A_i, Pinf = (x) Pinf_i, H = (x) H_i, state_dim = prod d_i.  Only the Product's own jitter is used
+    (the children's is ignored, as in the reference, whose Product inherits transition_statistics and initial_covariance).
+
+    Q follows the exact-Q rule: with M_i = A_i Pinf_i A_i^T (M_i = Pinf_i exactly for Constant and
+    HarmonicOscillator, and for trees of them), Q = (x) Pinf_i - (x) M_i, rewritten as (Pinf_g - M_g) (x) (x)_{i != g} Pinf_i when g is
+    the only child with M_g != Pinf_g, and exactly 0 when there is none."""
+
+    def __init__(self, kernels, jitter=0.0):
+        kernels = list(kernels)
+        assert kernels, "There must be at least one child kernel."
+        if not all(isinstance(k, StationaryKernel) for k in kernels):
+            raise TypeError("can only combine Kernel instances")
+        assert len(set(k.output_dim for k in kernels)) == 1, "All kernels must have the same output dimension"
+        self.kernels = kernels
+        self.state_dim = int(math.prod(k.state_dim for k in kernels))
+        super().__init__(kernels[0].output_dim, jitter)
+
+    @property
+    def feedback_matrix(self):
+        """(x) F_i, as the reference returns it.  NOT the generator of A = (x) expm(F_i dt): that is the Kronecker SUM
+        F_1 (+) F_2 = F_1 (x) I + I (x) F_2.  Nothing in the package reads it."""
+        F = self.kernels[0].feedback_matrix
+        for k in self.kernels[1:]:
+            F = _kron(F, k.feedback_matrix)
+        return F
+
+    def hyperparameter_leaves(self, device="cpu"):
+        return [k.hyperparameter_leaves(device) for k in self.kernels]
+
+    def _parts(self, dt, leaves=None):
+        lv = [None] * len(self.kernels) if leaves is None else leaves
+        parts = [k._parts(dt, l) for k, l in zip(self.kernels, lv)]
+        A, P = parts[0][0], parts[0][1]
+        for a, p, _, _ in parts[1:]:
+            A, P = _kron(A, a), _kron(P, p)
+        inexact = [i for i, pt in enumerate(parts) if not pt[3]]
+        if not inexact:
+            return A, P, torch.zeros_like(A), True
+        if len(inexact) == 1:
+            g = inexact[0]
+            Q = None
+            for i, (_, p, qt, _) in enumerate(parts):
+                f = qt if i == g else p
+                Q = f if Q is None else _kron(Q, f)
+            return A, P, Q, False
+        M = None
+        for a, p, _, ex in parts:
+            m = p if ex else a @ p @ a.transpose(-1, -2)
+            M = m if M is None else _kron(M, m)
+        return A, P, P - M, False
+
+    def _emission_row(self):
+        h = self.kernels[0]._emission_row()
+        for k in self.kernels[1:]:
+            h = torch.kron(h, k._emission_row())
+        return h
+
+    def _terms(self):
+        factors = []
+        for k in self.kernels:
+            t = k._terms()
+            if t is None or len(t) != 1:
+                return None     # a Sum child: not a product of primitive factors
+            factors.extend(t[0])
+        return [factors] if len(factors) <= 3 else None
