@@ -26,6 +26,7 @@
 #define MFGM_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -815,6 +816,35 @@ int mfgm_packed_sample(const mfgm_plan* plan, const double* L, const double* G, 
 #define MFGM_LIK_POISSON 2
 int mfgm_scalar_lik(int kind, size_t n, const double* fmu, const double* fvar, const double* y, double param, double* ve, double* g1,
                     double* g2, void* stream);
+
+/* ---- Power Expectation Propagation site update (sites on f, one scalar site per data point) --------------------------------------------
+ * Contract (fp64), per point i with posterior f-marginal (mu, v) = (fmu[i], fvar[i]), observation y = y[i], site (eta1, eta2, l) =
+ * (nat1[i], nat2[i], lnorm[i]) and power alpha in (0, 1]:
+ *   cavity (q(f) / t(f)^alpha):  lc = 1/v + 2 alpha eta2,  vc = 1/lc,  mc = vc (mu/v - alpha eta1)
+ *   tilted normaliser  log Z = log int p(y|f)^alpha N(f; mc, vc) df,  d1 = d log Z / d mc,  d2 = d^2 log Z / d mc^2:
+ *     kind MFGM_LIK_GAUSSIAN, param = variance s^2 > 0:  S = s^2/alpha + vc,
+ *        log Z = 1/2 (1 - alpha) log(2 pi s^2) - 1/2 log alpha + log N(y; mc, S),  d1 = (y - mc)/S,  d2 = -1/S
+ *     kind MFGM_LIK_BERNOULLI (param = jitter j, l(f) as mfgm_scalar_lik) at alpha == 1: log Z = log p_j(s mc / sqrt(1 + vc)) (exact)
+ *        and its analytic derivatives
+ *     kind MFGM_LIK_BERNOULLI at alpha != 1, kind MFGM_LIK_POISSON (param = bin size b) at any alpha: the 20-point Gauss-Hermite rule in
+ *        log space, X_k = mc + sqrt(2 vc) xi_k, pi_k = softmax_k(log W_k + alpha l(X_k)), log Z = logsumexp_k(log W_k + alpha l(X_k)),
+ *        d1 = sum_k pi_k alpha l'_k,  d2 = sum_k pi_k (alpha l''_k + (alpha l'_k)^2) - d1^2  (the derivatives of the rule);
+ *        Bernoulli l'' = -X l' - l'^2, Poisson l' = y - b e^X, l'' = -b e^X
+ *   update:  L2 = 1/2 / (vc + 1/d2),  L1 = 2 L2 (d1/d2 - mc),  e = log Z + n(mc, vc) - n(mu, v),  n(m, v) = 1/2 (log v + m^2/v)
+ *            eta1 <- (1 - lr) eta1 + lr ((1 - alpha) eta1 + L1),  eta2 <- ... + L2,  l <- (1 - lr) l + lr ((1 - alpha) l + e)
+ * A point with v <= 0, lc <= 0, or a non-finite L1 or L2 keeps its site, gets e = NaN, and adds 1 to *skipped (int32, device; may be
+ * null).  The update covers idx[0 .. k) (int64, device) or all n points when idx is null (k is then ignored); entries of idx outside
+ * [0, n) are ignored, and the caller gives each point at most once.  nat1, nat2 [n] are read always and written only when lr != 0;
+ * lnorm [n] (may be null: neither read nor written) likewise; e_out [n] (may be null) receives e at the selected points.  lr = 0 with
+ * e_out is the energy mode: nothing but e_out is written.  One lane per selected point; no host synchronisation, no allocation
+ * (graph-capturable).  Returns 1 for an unknown kind, a param out of range, alpha outside (0, 1], lr outside [0, 1], or a missing fmu,
+ * fvar, y, nat1, nat2 when there is a point to cover.
+ * mfgm_pep_tilted: log Z, d1, d2 [n] (each may be null) of the same kinds at given cavities mc, vc, y [n]. */
+#define MFGM_LIK_GAUSSIAN 3
+int mfgm_pep_sites(int kind, size_t n, const double* fmu, const double* fvar, const double* y, double param, double alpha, double lr,
+                   const int64_t* idx, size_t k, double* nat1, double* nat2, double* lnorm, double* e_out, int* skipped, void* stream);
+int mfgm_pep_tilted(int kind, size_t n, const double* mc, const double* vc, const double* y, double param, double alpha, double* lz,
+                    double* d1, double* d2, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ VEC, FULL, SYM, TRI = 0, 1, 2, 3
 # mfgm_kernel_terms factor kinds (include/mfgm.h)
 FACTOR_MATERN12, FACTOR_MATERN32, FACTOR_MATERN52, FACTOR_CONSTANT, FACTOR_HARMONIC = 1, 2, 3, 4, 5
 # mfgm_scalar_lik kinds (include/mfgm.h)
-LIK_BERNOULLI, LIK_POISSON = 1, 2
+LIK_BERNOULLI, LIK_POISSON, LIK_GAUSSIAN = 1, 2, 3
 
 _lib = None
 
@@ -145,6 +145,10 @@ EXPORTS = {
     "mfgm_packed_sample_scratch_doubles": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int]),
     "mfgm_packed_sample": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_uint] + [ctypes.c_void_p] * 3),
     "mfgm_scalar_lik": (ctypes.c_int, [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 4),
+    "mfgm_pep_sites": (ctypes.c_int, [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_double] * 3
+                       + [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 6),
+    "mfgm_pep_tilted": (ctypes.c_int, [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_double] * 2
+                        + [ctypes.c_void_p] * 4),
 }
 
 

@@ -275,3 +275,142 @@ class Poisson(ScalarQuadratureLikelihood):
         """Exact moments of y: m = b e^{mu + v/2}, m + (e^v - 1) m^2 (gpflow takes them by quadrature)."""
         m = self.binsize * torch.exp(f_means + 0.5 * f_vars)
         return m, m + torch.expm1(f_vars) * m * m
+
+
+# ---- Power Expectation Propagation wrappers (markovflow/likelihoods/likelihoods.py:149-275), with the power applied ---------------------
+class PEPScalarLikelihood:
+    """A scalar likelihood `base` wrapped for Power Expectation Propagation: the tilted normaliser
+        log Z = log int p(y | f)^alpha N(f; Fmu, Fvar) df
+    and its first two derivatives with respect to Fmu (include/mfgm.h, mfgm_pep_tilted).  Unlike the reference, whose
+    log_expected_density ignores alpha, the power is applied: with the exact power the EP fixed point of a Gaussian likelihood is its
+    exact site for every alpha.
+
+    `base` is Gaussian, Bernoulli, Poisson or any ScalarQuadratureLikelihood.  log Z is the n_gh-point Gauss-Hermite rule in log space
+    (gpflow's quadrature.logspace), except for Bernoulli at alpha = 1, where it is the closed form the reference uses
+    (base.predict_log_density).  The native route (one launch of mfgm_pep_tilted) runs when the base has a kind, the tensors are
+    contiguous fp64 on the device, n_gh == 20 and nothing asks for a gradient; otherwise the torch route (the same formula, its
+    derivatives by autograd twice, what the reference's nested GradientTape gives) runs, on any device.
+    Shapes: Fmu, Fvar, Y [..., n, 1]; log Z [..., n]; d1, d2 [..., n, 1]."""
+
+    def __init__(self, base, num_gauss_hermite_points=20):
+        import numpy as np
+        self.base = base
+        self.num_gauss_hermite_points = self.n_gh = int(num_gauss_hermite_points)
+        xi, w = np.polynomial.hermite.hermgauss(self.n_gh)
+        self._xi, self._logw = xi, np.log(w / math.sqrt(math.pi))
+        self._rule_cache = {}
+
+    @property
+    def kind(self):
+        """mfgm_pep_tilted / mfgm_pep_sites kind of the native route, None when the base has none."""
+        return getattr(self.base, "kind", None)
+
+    @property
+    def param(self):
+        return self.base.param
+
+    def _base_log_prob(self, F, Y):
+        if isinstance(self.base, Gaussian):
+            v = self.base.variance
+            return -0.5 * math.log(2.0 * math.pi * v) - 0.5 * (Y - F) ** 2 / v
+        return self.base.log_prob(F, Y)
+
+    def _rule(self, like):
+        key = str(like.device)
+        r = self._rule_cache.get(key)
+        if r is None:
+            r = self._rule_cache[key] = (torch.tensor(self._xi, dtype=torch.float64, device=like.device),
+                                         torch.tensor(self._logw, dtype=torch.float64, device=like.device))
+        return r
+
+    def _log_z_torch(self, Fmu, Fvar, Y, alpha):
+        """log Z [..., n, 1] (differentiable)."""
+        if isinstance(self.base, Bernoulli) and alpha == 1.0:
+            x = Fmu / torch.sqrt(1.0 + Fvar)
+            return torch.log(self.base._p(torch.where(Y == 1, x, -x)))
+        xi, logw = self._rule(Fmu)
+        X = Fmu[..., None] + math.sqrt(2.0) * torch.sqrt(Fvar)[..., None] * xi
+        return torch.logsumexp(alpha * self._base_log_prob(X, Y[..., None]) + logw, dim=-1)
+
+    def _native(self, Fmu, Fvar, Y):
+        if self.kind is None or self.n_gh != 20 or not Fmu.is_cuda:
+            return False
+        ts = (Fmu, Fvar, Y)
+        if any(t.requires_grad for t in ts) and torch.is_grad_enabled():
+            return False
+        return all(t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.shape == Fmu.shape for t in ts)
+
+    def _launch(self, Fmu, Fvar, Y, alpha, want_grads):
+        from . import _lib
+        from .packed import _ptr, _stream
+        mk = lambda: torch.empty(Fmu.shape, dtype=torch.float64, device=Fmu.device)
+        lz = mk()
+        d1, d2 = (mk(), mk()) if want_grads else (None, None)
+        _lib.check(_lib.load().mfgm_pep_tilted(self.kind, Fmu.numel(), _ptr(Fmu), _ptr(Fvar), _ptr(Y), float(self.param), float(alpha),
+                                               _ptr(lz), _ptr(d1), _ptr(d2), _stream()), "mfgm_pep_tilted")
+        return lz, d1, d2
+
+    def log_expected_density(self, Fmu, Fvar, Y, alpha=1.0):
+        """log int p(y = Y | f)^alpha N(f; Fmu, Fvar) df, [..., n]."""
+        if self._native(Fmu, Fvar, Y):
+            return self._launch(Fmu, Fvar, Y, alpha, False)[0][..., 0]
+        return self._log_z_torch(Fmu, Fvar, Y, alpha)[..., 0]
+
+    def grad_log_expected_density(self, Fmu, Fvar, Y, alpha=1.0):
+        """(log Z [..., n], (d log Z / d Fmu, d^2 log Z / d Fmu^2) [..., n, 1] each)."""
+        if self._native(Fmu, Fvar, Y):
+            lz, d1, d2 = self._launch(Fmu, Fvar, Y, alpha, True)
+            return lz[..., 0], (d1, d2)
+        with torch.enable_grad():
+            mu = Fmu.detach().requires_grad_(True)
+            lz = self._log_z_torch(mu, Fvar.detach(), Y.detach(), alpha)
+            (d1,) = torch.autograd.grad(lz.sum(), [mu], create_graph=True)
+            (d2,) = torch.autograd.grad(d1.sum(), [mu])
+        return lz.detach()[..., 0], (d1.detach(), d2)
+
+    def predict_log_density(self, f_means, f_vars, observations):
+        """The base likelihood's log predictive density, [..., n] (log N(y; mu, v + s^2) for a Gaussian base)."""
+        if isinstance(self.base, Gaussian):
+            v = f_vars + self.base.variance
+            return (-0.5 * torch.log(2.0 * math.pi * v) - 0.5 * (observations - f_means) ** 2 / v).sum(-1)
+        return self.base.predict_log_density(f_means, f_vars, observations)
+
+    def predict_mean_and_var(self, f_means, f_vars):
+        return self.base.predict_mean_and_var(f_means, f_vars)
+
+
+class PEPGaussian(PEPScalarLikelihood):
+    """The Gaussian likelihood N(y; f, s^2) with the tilted normaliser in closed form and the exact power:
+        log Z = 1/2 (1 - alpha) log(2 pi s^2) - 1/2 log alpha + log N(y; Fmu, s^2/alpha + Fvar)
+    (the reference's alpha log N(y; Fmu, s^2 + Fvar) is not this integral unless alpha = 1).  Native kind MFGM_LIK_GAUSSIAN."""
+
+    def __init__(self, base):
+        if not isinstance(base, Gaussian):
+            raise TypeError("PEPGaussian wraps a Gaussian likelihood")
+        super().__init__(base, num_gauss_hermite_points=20)
+
+    @property
+    def kind(self):
+        from ._lib import LIK_GAUSSIAN
+        return LIK_GAUSSIAN
+
+    @property
+    def param(self):
+        return self.base.variance
+
+    def _terms(self, Fmu, Fvar, Y, alpha):
+        s2 = self.base.variance
+        S = s2 / alpha + Fvar
+        r = Y - Fmu
+        lz = (0.5 * (1.0 - alpha) * math.log(2.0 * math.pi * s2) - 0.5 * math.log(alpha) - 0.5 * torch.log(2.0 * math.pi * S)
+              - 0.5 * r * r / S)
+        return lz, r / S, -1.0 / S
+
+    def _log_z_torch(self, Fmu, Fvar, Y, alpha):
+        return self._terms(Fmu, Fvar, Y, alpha)[0]
+
+    def grad_log_expected_density(self, Fmu, Fvar, Y, alpha=1.0):
+        if self._native(Fmu, Fvar, Y):
+            return super().grad_log_expected_density(Fmu, Fvar, Y, alpha)
+        lz, d1, d2 = self._terms(Fmu, Fvar, Y, alpha)
+        return lz[..., 0], (d1, d2)

@@ -185,6 +185,16 @@ class StateSpaceModel:
         kl = 0.5 * (tr + mh - dim + 2.0 * pp["sumlogchol"] - 2.0 * self._precision_packed()["sumlogchol"])
         return self._unflat(kl)
 
+    def normalizer(self):
+        """1/2 (dim log 2 pi - log det Lambda + |L^T mu|^2), Lambda = L L^T the precision (state_space_model.py:595-609); shape
+        batch_shape, on the device.  One factorisation of the precision with its right-hand side Lambda mu: y = L^{-1} Lambda mu = L^T mu,
+        so log det Lambda and |L^T mu|^2 are the factorisation's logdet and quad outputs."""
+        import math
+        pr = self._precision_packed()
+        f = self.plan.factor(pr["diag"], pr["sub"], pr["lin"], want_logdet=True, want_quad=True, store_G=self.plan.wide)
+        dim = float(self.T * self.d)
+        return self._unflat(0.5 * dim * math.log(2.0 * math.pi) - f["logdet"] + 0.5 * f["quad"])
+
 
 def _ssm_sample(self, sample_shape, generator=None, *, seed=None, stream=1):
     """
