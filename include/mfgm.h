@@ -846,6 +846,30 @@ int mfgm_pep_sites(int kind, size_t n, const double* fmu, const double* fvar, co
 int mfgm_pep_tilted(int kind, size_t n, const double* mc, const double* vc, const double* y, double param, double alpha, double* lz,
                     double* d1, double* d2, void* stream);
 
+/* ---- Sparse Power Expectation Propagation (sites on pairs of consecutive inducing states; csrc/mfgm_spep.h) ----------------------------
+ * Contract (fp64).  data, mu [M, d], Sig [M, d, d], Sub [M, d, d] as mfgm_sparse_predict takes them; interval m = 0..M holds the n_m data
+ * points seg[m] .. seg[m+1], its pair marginal N(mu_m, S_m) over v_m = (state m-1, state m) is assembled from the marginal blocks (the
+ * prior's initial mean / covariance at both ends, zero cross block there); site (nat1 [M+1, 2d], nat2 [M+1, 2d, 2d] symmetric,
+ * lnorm [M+1]); kind / param / alpha and the tilted moments as mfgm_pep_sites.  Per interval with n_m > 0, beta = alpha / n_m:
+ *   Lam = S_m^-1,  h = Lam mu_m,  g_q = 1/2 (log det S_m + mu_m^T h)
+ *   Lam_c = Lam + 2 beta nat2_m,  hc = h - beta nat1_m,  Sc = Lam_c^-1,  muc = Sc hc,  g_c = 1/2 (-log det Lam_c + hc^T muc)
+ *   per point i of the interval:  mc = w_i^T muc,  s = w_i^T Sc w_i,  (log Z, d1, d2) at the cavity N(mc, s + c_i),
+ *     L2 = 1/2 / (s + 1/d2),  L1 = 2 L2 (d1/d2 - mc),  e_i = log Z + g_c - g_q
+ *   X <- (1 - lr) X + lr ((1 - alpha) X + sum_i dX_i)  for X = (nat1, nat2, lnorm), dX_i = (L1 w_i, L2 w_i w_i^T, e_i)
+ * An interval without data takes the update with an empty sum and e = 0.  An interval whose S_m or Lam_c is not positive definite keeps
+ * its site and lnorm bit for bit, gets e = NaN and adds n_m to *skipped; a point with a non-finite L1 or L2 contributes nothing and adds 1.
+ * e_out [M+1] (may be null) receives sum_{i in m} e_i; lnorm and skipped (int32, device) may be null.  lr = 0 is the energy mode:
+ * nothing but e_out is written.  No host synchronisation, no allocation (graph-capturable); one wavefront per 64 / 2d' intervals
+ * (2d' = 2d rounded up to a power of two), d <= 32.  Returns 1 for an unknown kind, a param out of range, alpha outside (0, 1],
+ * lr outside [0, 1], an invalid data description or a missing pointer.
+ * mfgm_sparse_pep_sites_q: the same on the quadrant-packed nat2q [M+1, d (d + 1) + d^2] (mfgm_sparse_factor_q). */
+int mfgm_sparse_pep_sites(const mfgm_sparse_data* data, int kind, const double* y, double param, double alpha, double lr, const double* mu,
+                          const double* Sig, const double* Sub, double* nat1, double* nat2, double* lnorm, double* e_out, int* skipped,
+                          void* stream);
+int mfgm_sparse_pep_sites_q(const mfgm_sparse_data* data, int kind, const double* y, double param, double alpha, double lr,
+                            const double* mu, const double* Sig, const double* Sub, double* nat1, double* nat2q, double* lnorm,
+                            double* e_out, int* skipped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

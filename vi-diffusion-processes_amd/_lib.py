@@ -149,6 +149,10 @@ EXPORTS = {
                        + [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 6),
     "mfgm_pep_tilted": (ctypes.c_int, [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [ctypes.c_double] * 2
                         + [ctypes.c_void_p] * 4),
+    "mfgm_sparse_pep_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_double] * 3
+                              + [ctypes.c_void_p] * 9),
+    "mfgm_sparse_pep_sites_q": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_double] * 3
+                                + [ctypes.c_void_p] * 9),
 }
 
 
