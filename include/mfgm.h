@@ -870,6 +870,35 @@ int mfgm_sparse_pep_sites_q(const mfgm_sparse_data* data, int kind, const double
                             const double* mu, const double* Sig, const double* Sub, double* nat1, double* nat2q, double* lnorm,
                             double* e_out, int* skipped, void* stream);
 
+/* ---- spatio-temporal sparse CVI (markovflow/models/spatio_temporal_variational.py:360-586; csrc/mfgm_st.h) -------------------------------
+ * Sparse CVI on pairs of inducing states whose state is Ms independent copies of a time kernel of state dimension dt, one per spatial
+ * inducing point: D = Ms dt, 9 <= D <= 32, state layout [copy j][component k].  The projection of data point i = (x_i, t_i) onto the
+ * pair of inducing states around t_i is the Kronecker product  w_i[half D + j dt + k] = a_i[j] h_i[half dt + k]  of
+ * a_i = chol(K_s(Z_s, Z_s))^-1 k_s(Z_s, x_i) and h_i = H_t P^t_i (conditionals.py:207-256 on the time kernel alone); c_i is the
+ * conditional variance of f(x_i, t_i) given the pair.  seg, the intervals and the prior padding are those of mfgm_sparse_data (one
+ * process: every interval).  The two passes below are mfgm_sparse_predict_kl and mfgm_sparse_site_update_q with w_i = a_i (x) h_i
+ * rebuilt on chip: (Ms + 2 dt + 3) instead of (2 D + 3) doubles of traffic per point and pass.  All pointers are device pointers. */
+typedef struct mfgm_st_data {
+    int M, Ms, dt, N;           /* time inducing states, spatial inducing points, time-kernel state dimension, data points */
+    const int* seg;             /* [M + 2] CSR offsets of the data points per interval */
+    const double* a;            /* [N, Ms]   */
+    const double* h;            /* [N, 2 dt] */
+    const double* c;            /* [N]       */
+    const double* prior_mean;   /* [D]    */
+    const double* prior_cov;    /* [D, D] */
+} mfgm_st_data;
+/* fmu_i = w_i^T E[v], fvar_i = w_i^T Cov[v] w_i + c_i from the marginals mu [M, D], Sig [M, D, D], Sub [M, D, D] (as
+ * mfgm_sparse_predict); with plan, trace and maha all non-null also the trace / Mahalanobis terms of KL[q || p] exactly as
+ * mfgm_sparse_predict_kl takes them (then Pd, Ps, mup and ws are required), otherwise the plain prediction.  Returns 1 for D outside
+ * 9 .. 32 (Ms or dt outside 1 .. 32 included), a missing pointer or a plan of another shape. */
+int mfgm_st_predict_kl(const mfgm_st_data* data, const double* mu, const double* Sig, const double* Sub, double* fmu, double* fvar,
+                       const mfgm_plan* plan, const double* Pd, const double* Ps, double aD, double aS, const double* mup, double* trace,
+                       double* maha, void* ws, void* stream);
+/* sites <- (1 - lr) sites + lr sum_{i in interval} (g1_i w_i, g2_i w_i w_i^T) on nat1 [M + 1, 2D] and the quadrant-packed
+ * nat2q [M + 1, D (D + 1) + D^2], in place; one owner per entry, no atomics. */
+int mfgm_st_site_update_q(const mfgm_st_data* data, const double* g1, const double* g2, double lr, double* nat1, double* nat2q,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,257 @@
+"""
+Host tests of the spatio-temporal sparse CVI model (vidp_amd.spatio_temporal_variational.SpatioTemporalSparseCVI) on its torch route
+with CPU tensors: the known answer of the reference's own test_spatiotemporalsparsecvi (data on the grid Z_s x Z_t, Gaussian
+likelihood: the model is exact GP regression with k_s k_t), off-grid Bernoulli / Poisson runs against the dense NumPy model of
+tests/np_st.py, the Kronecker projection against the reference's construction, the multi-output kernel against Sum, argument checks
+of the model and of the two C entry points (which return before any launch).
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import np_kernels
+from tests import np_lik, np_st
+
+
+T = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+
+
+def _grid(zs, zt):
+    """Every (x, t) of the grid, sorted by time; zs [Ms, p]."""
+    X = np.concatenate([np.repeat(zs[None], len(zt), 0), np.repeat(zt[:, None, None], len(zs), 1)], axis=-1)
+    return X.reshape(-1, zs.shape[1] + 1)
+
+
+def _linear_mean(X):
+    w = np.arange(1.0, X.shape[1] + 1.0)
+    return (X @ (T(w) if torch.is_tensor(X) else w))[:, None] + 3.0
+
+
+def _time_cov(name, ls, var):
+    def k(tau):
+        r = np.abs(tau) / ls
+        if name == "matern12":
+            return var * np.exp(-r)
+        return var * (1.0 + np.sqrt(3.0) * r) * np.exp(-np.sqrt(3.0) * r)
+    return k
+
+
+@pytest.mark.parametrize("case", ["reference", "wide", "wide_mean"])
+def test_known_answer_on_the_grid(case):
+    """Data on Z_s x Z_t, Gaussian likelihood, learning_rate 1, ten update_sites: elbo and space_time_predict_f at the data equal dense
+    GP regression with k_s k_t (log marginal likelihood and posterior mean by NumPy Cholesky), atol = rtol = 1e-6 as in the reference.
+    reference: Ms = 2, Matern-1/2 in time, 2 times, linear mean X @ [1, 2]^T + 3 (the reference's own test).  wide: Ms = 5,
+    Matern-3/2 in time (D = 10), 40 times 0.25 lengthscales apart, spatial Matern-3/2 with Z_s 0.5 lengthscales apart."""
+    from vidp_amd import kernels as K, space_kernels as SK
+    from vidp_amd.likelihoods import Gaussian
+    from vidp_amd.spatio_temporal_variational import SpatioTemporalSparseCVI
+    rng = np.random.default_rng(42)
+    if case == "reference":
+        zs, zt = np.array([[0.0], [1.0]]), np.array([2.0, 3.0])
+        kt, ktc, mean = K.Matern12(1.0, 1.0), _time_cov("matern12", 1.0, 1.0), _linear_mean
+    else:
+        zs, zt = 0.5 * np.arange(5.0)[:, None], 0.25 * np.arange(40.0)
+        kt, ktc, mean = K.Matern32(1.0, 1.0), _time_cov("matern32", 1.0, 1.0), (_linear_mean if case == "wide_mean" else None)
+    X = _grid(zs, zt)
+    Y = rng.normal(size=(X.shape[0], 1)) + (0.0 if mean is None else mean(X))
+    m = SpatioTemporalSparseCVI(T(zs), T(zt), SK.Matern32(1.0, 1.0), kt, Gaussian(1.0), mean_function=mean, learning_rate=1.0)
+    data = (T(X), T(Y))
+    for _ in range(10):
+        m.update_sites(data)
+    lml, post_mean = np_st.gpr(np_st.SpaceKernel("matern32", 1.0, 1.0), ktc, X, Y, 1.0, mean)
+    got = float(m.elbo(data))
+    print(f"known answer {case}: elbo {got!r} log marginal likelihood {lml!r}")
+    assert np.allclose(got, lml, atol=1e-6, rtol=1e-6)
+    assert np.allclose(m.space_time_predict_f(data[0])[0].numpy()[:, 0], post_mean, atol=1e-6, rtol=1e-6)
+    assert float(m.loss(data)) == -float(m.classic_elbo(data))
+
+
+def _offgrid(rng, kind, Ms, M, N, p=2):
+    zs = rng.uniform(-1.0, 1.0, size=(Ms, p))
+    zt = np.linspace(0.0, 0.4 * (M - 1), M)
+    X = np.concatenate([rng.uniform(-1.2, 1.2, size=(N, p)), np.sort(rng.uniform(-0.3, zt[-1] + 0.3, size=N))[:, None]], axis=1)
+    f = 1.2 * np.sin(0.8 * X[:, -1]) * np.cos(X[:, 0])
+    y = (f + 0.5 * rng.normal(size=N) > 0).astype(np.float64) if kind == "bernoulli" else rng.poisson(np.exp(0.5 * f)).astype(np.float64)
+    return zs, zt, X, y[:, None]
+
+
+@pytest.mark.parametrize("kind", ["bernoulli", "poisson"])
+def test_offgrid_against_dense_numpy(kind):
+    """Off-grid data, twenty damped steps (lr = 0.5): sites, elbo, space_time_predict_f and predict_log_density against tests/np_st.py
+    at the project's model-level 1e-8 (README: config 5 in miniature over damped steps).  Ms = 5, Matern-3/2 in time (D = 10)."""
+    from vidp_amd import kernels as K, space_kernels as SK
+    from vidp_amd.likelihoods import Bernoulli, Poisson
+    from vidp_amd.spatio_temporal_variational import SpatioTemporalSparseCVI
+    rng = np.random.default_rng(7)
+    zs, zt, X, y = _offgrid(rng, kind, 5, 12, 70)
+    var = 1.0 if kind == "bernoulli" else 0.25
+    lik, olik = (Bernoulli(1e-3), np_lik.Bernoulli(1e-3)) if kind == "bernoulli" else (Poisson(1.3), np_lik.Poisson(1.3))
+    m = SpatioTemporalSparseCVI(T(zs), T(zt), SK.SquaredExponential([0.8, 1.1], 1.0), K.Matern32(1.5, var), lik, learning_rate=0.5)
+    o = np_st.SpatioTemporalSparseCVI(zs, zt, np_st.SpaceKernel("se", [0.8, 1.1], 1.0), np_kernels.Matern32(1.5, var), olik,
+                                      learning_rate=0.5)
+    data = (T(X), T(y))
+    tol = 1e-8
+    for _ in range(20):
+        m.update_sites(data)
+        o.update_sites(X, y)
+        np.testing.assert_allclose(m.nat1.numpy(), o.nat1, rtol=tol, atol=tol * np.abs(o.nat1).max())
+        np.testing.assert_allclose(m.nat2.numpy(), o.nat2, rtol=tol, atol=tol * np.abs(o.nat2).max())
+        np.testing.assert_allclose(float(m.elbo(data)), o.elbo(X, y), rtol=tol)
+    fm, fv = m.space_time_predict_f(data[0])
+    om, ov = o.predict_f(X)
+    np.testing.assert_allclose(fm.numpy(), om, rtol=tol, atol=tol)
+    np.testing.assert_allclose(fv.numpy(), ov, rtol=tol, atol=tol)
+    np.testing.assert_allclose(m.predict_log_density(data).numpy(), o.predict_log_density(X, y), rtol=tol, atol=tol)
+    assert m._packed and m.nat2.shape == (13, 20, 20)
+
+
+def test_projection_matches_the_reference_construction():
+    """w built from (a, h) equals state_to_space_conditional_projection @ P with P the conditional statistics of the FULL kernel
+    (projection_inducing_states_to_observations, reference :494-507), to 1e-13."""
+    from vidp_amd import kernels as K, space_kernels as SK
+    from vidp_amd.likelihoods import Gaussian
+    from vidp_amd.sparse_pep import _cond_stats
+    from vidp_amd.spatio_temporal_variational import SpatioTemporalSparseCVI
+    rng = np.random.default_rng(3)
+    for kt in (K.Matern12(0.7, 1.3), K.Matern32(1.5, 0.8), K.Matern52(1.1, 1.2)):
+        zs, zt, X, _ = _offgrid(rng, "bernoulli", 4, 9, 40)
+        m = SpatioTemporalSparseCVI(T(zs), T(zt), SK.Matern52([0.9, 1.4], 1.7), kt, Gaussian(1.0))
+        P, _, _ = _cond_stats(T(X[:, -1]), T(zt), m.kernel)
+        A = m.kernel.state_to_space_conditional_projection(T(X))
+        want = torch.einsum("ncs,nfc->nfs", P, A)
+        got = m.projection_inducing_states_to_observations((T(X), None))
+        assert got.shape == (40, 1, 2 * 4 * kt.state_dim) and A.shape == (40, 1, 4 * kt.state_dim)
+        np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=1e-13, atol=1e-13)
+        a, resid = m.kernel.spatial_features(T(X[:, :-1]))
+        L = np.linalg.cholesky(np_st.SpaceKernel("matern52", [0.9, 1.4], 1.7).K(zs))
+        np.testing.assert_allclose(a.numpy(), np.linalg.solve(L, np_st.SpaceKernel("matern52", [0.9, 1.4], 1.7).K(zs, X[:, :-1])).T,
+                                   rtol=1e-12, atol=1e-13)
+        np.testing.assert_allclose(resid.numpy(), 1.7 - (a.numpy() ** 2).sum(-1), rtol=1e-13, atol=1e-13)
+        H = m.kernel.generate_emission_model(T(zt)).emission_matrix
+        assert H.shape == (9, 4, 4 * kt.state_dim)
+        np.testing.assert_allclose(H[0].numpy(), L @ np.kron(np.eye(4), kt._emission_row().numpy()[None]), rtol=1e-13, atol=1e-14)
+
+
+def test_space_kernels():
+    from vidp_amd import space_kernels as SK
+    rng = np.random.default_rng(5)
+    X, X2 = rng.normal(size=(7, 3)), rng.normal(size=(4, 3))
+    for name, cls in (("se", SK.SquaredExponential), ("matern12", SK.Matern12), ("matern32", SK.Matern32), ("matern52", SK.Matern52)):
+        for ls in (0.7, [0.5, 1.0, 2.0]):
+            k, o = cls(ls, 1.9), np_st.SpaceKernel(name, ls, 1.9)
+            np.testing.assert_allclose(k.K(T(X)).numpy(), o.K(X), rtol=1e-13, atol=1e-14)
+            np.testing.assert_allclose(k.K(T(X), T(X2)).numpy(), o.K(X, X2), rtol=1e-13, atol=1e-14)
+            np.testing.assert_allclose(k.K_diag(T(X)).numpy(), np.full(7, 1.9))
+    with pytest.raises(ValueError):
+        SK.Matern32(-1.0, 1.0)
+    with pytest.raises(ValueError):
+        SK.Matern32([1.0, 2.0], 1.0).K(T(X))
+
+
+def test_independent_multi_output_prior_is_sums():
+    """The prior state-space model of IndependentMultiOutput equals Sum's on the same children; the emission is block-diagonal."""
+    from vidp_amd import kernels as K
+    kids = [K.Matern32(0.8, 1.2), K.Matern12(1.5, 0.7), K.Matern52(1.1, 2.0)]
+    imo, s = K.IndependentMultiOutput(kids), K.Sum(kids)
+    assert imo.state_dim == s.state_dim == 6 and imo.output_dim == 3 and s.output_dim == 1
+    dt = T(np.array([0.0, 0.1, 0.7, 3.0]))
+    for x, y in zip(imo.transition_statistics_local(dt), s.transition_statistics_local(dt)):
+        assert torch.equal(x, y)
+    assert torch.equal(imo.initial_covariance_matrix(), s.initial_covariance_matrix())
+    assert torch.equal(imo.feedback_matrix, s.feedback_matrix) and torch.equal(imo.state_mean, s.state_mean)
+    assert imo._components() == s._components()
+    em = imo.generate_emission_model(T(np.arange(5.0)))
+    assert em.emission_matrix.shape == (5, 3, 6) and em.output_dim == 3
+    want = np.zeros((3, 6))
+    want[0, 0] = want[1, 2] = want[2, 3] = 1.0
+    np.testing.assert_array_equal(em.constant_matrix.numpy(), want)
+    np.testing.assert_array_equal(em.emission_matrix[3].numpy(), want)
+    np.testing.assert_array_equal(want.sum(0), s._emission_row().numpy())
+
+
+def test_argument_validation():
+    from vidp_amd import kernels as K, space_kernels as SK
+    from vidp_amd.likelihoods import Gaussian
+    import vidp_amd
+    cls = vidp_amd.SpatioTemporalSparseCVI
+    zs, zt = T(np.arange(3.0)[:, None]), T(np.arange(4.0))
+    ks, kt, lik = SK.Matern32(1.0, 1.0), K.Matern32(1.0, 1.0), Gaussian(1.0)
+    with pytest.raises(NotImplementedError, match="shard"):
+        cls(zs, zt, ks, kt, lik, shard=(0, 2))
+    with pytest.raises(NotImplementedError, match="num_data"):
+        cls(zs, zt, ks, kt, lik, num_data=100)
+    with pytest.raises(NotImplementedError, match="batched"):
+        cls(zs, zt[None].repeat(2, 1), ks, kt, lik)
+    with pytest.raises(NotImplementedError, match="batched"):
+        cls(zs[None].repeat(2, 1, 1), zt, ks, kt, lik)
+    with pytest.raises(ValueError, match=r"Ms \* d_t = 11 \* 3 = 33 exceeds the limit of 32"):
+        cls(T(np.arange(11.0)[:, None]), zt, ks, K.Matern52(1.0, 1.0), lik)
+    with pytest.raises(ValueError, match="callable"):
+        cls(zs, zt, ks, kt, lik, mean_function=3.0)
+
+    class Varying(K.Matern32):
+        def generate_emission_model(self, time_points):
+            em = super().generate_emission_model(time_points)
+            em.constant_matrix = None
+            return em
+
+    with pytest.raises(NotImplementedError, match="time-invariant"):
+        cls(zs, zt, ks, Varying(1.0, 1.0), lik)
+    m = cls(zs, zt, ks, kt, lik)
+    assert m.inducing_time is zt and torch.equal(m.inducing_space, zs) and m.kernel.state_dim == 6 and m.likelihood is lik
+    with pytest.raises(ValueError, match="time in the last column"):
+        m.space_time_predict_f(zt)
+    with pytest.raises(NotImplementedError, match="device"):
+        m.dist_q
+
+
+def test_entry_points_check_their_arguments_without_a_gpu():
+    """mfgm_st_predict_kl / mfgm_st_site_update_q return 1 before any launch for D outside 9 .. 32, factors that would overflow the
+    packed layout and missing pointers."""
+    import vidp_amd
+    lib = vidp_amd._lib.load()
+    one = ctypes.c_void_p(8)          # a non-null pointer that is never dereferenced: every call below fails its checks first
+
+    def st(Ms, dt, M=4, N=3, seg=one, a=one, h=one, c=one, pm=one, pc=one):
+        s = vidp_amd._lib.StData()
+        s.M, s.Ms, s.dt, s.N = M, Ms, dt, N
+        s.seg, s.a, s.h, s.c, s.prior_mean, s.prior_cov = seg, a, h, c, pm, pc
+        return s
+
+    def predict(s, mu=one, fvar=one):
+        return lib.mfgm_st_predict_kl(ctypes.byref(s), mu, one, one, one, fvar, None, None, None, -2.0, -1.0, None, None, None, None, None)
+
+    def update(s, g1=one, nat2q=one):
+        return lib.mfgm_st_site_update_q(ctypes.byref(s), g1, one, 0.5, one, nat2q, None)
+
+    for Ms, dt in ((4, 2), (2, 3), (1, 1), (11, 3), (17, 2), (33, 1), (1, 33), (0, 9), (9, 0), (-3, -3), (65536, 65536), (2 ** 30, 4)):
+        assert predict(st(Ms, dt)) == 1 and update(st(Ms, dt)) == 1, (Ms, dt)
+    for bad in (dict(seg=None), dict(a=None), dict(h=None), dict(c=None), dict(M=0), dict(N=-1)):
+        assert predict(st(5, 2, **bad)) == 1 and update(st(5, 2, **bad)) == 1, bad
+    assert predict(st(5, 2, pm=None)) == 1 and predict(st(5, 2, pc=None)) == 1
+    assert predict(st(5, 2), mu=None) == 1 and predict(st(5, 2), fvar=None) == 1
+    assert update(st(5, 2), g1=None) == 1 and update(st(5, 2), nat2q=None) == 1
+    assert lib.mfgm_st_predict_kl(None, one, one, one, one, one, None, None, None, -2.0, -1.0, None, None, None, None, None) == 1
+    assert lib.mfgm_st_site_update_q(None, one, one, 0.5, one, one, None) == 1
+    # no data and no KL terms asked for: nothing to do
+    assert predict(st(5, 2, N=0, a=None, h=None, c=None)) == 0
+
+
+def test_torch_prediction_in_chunks():
+    """The torch route gathers the pair covariances PREDICT_CHUNK points at a time: the result does not depend on the chunk."""
+    from vidp_amd import kernels as K, space_kernels as SK
+    from vidp_amd.likelihoods import Bernoulli
+    from vidp_amd.spatio_temporal_variational import SpatioTemporalSparseCVI
+    rng = np.random.default_rng(11)
+    zs, zt, X, y = _offgrid(rng, "bernoulli", 3, 8, 50)
+    m = SpatioTemporalSparseCVI(T(zs), T(zt), SK.Matern32(1.0, 1.0), K.Matern32(1.5, 1.0), Bernoulli(1e-3), learning_rate=0.5)
+    data = (T(X), T(y))
+    for _ in range(3):
+        m.update_sites(data)
+    fm, fv = m.space_time_predict_f(data[0])
+    m.PREDICT_CHUNK = 7
+    gm, gv = m.space_time_predict_f(data[0])
+    assert torch.equal(fm, gm)
+    np.testing.assert_allclose(gv.numpy(), fv.numpy(), rtol=1e-14, atol=0)

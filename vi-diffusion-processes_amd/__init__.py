@@ -7,3 +7,11 @@ interface names; compute happens in hand-written HIP kernels (csrc/) reached thr
 from . import _lib  # noqa: F401
 from .packed import Plan  # noqa: F401
 from ._lib import FULL, SYM, TRI, VEC  # noqa: F401
+
+
+def __getattr__(name):
+    # the models import the kernels and the plan machinery: loaded on first use
+    if name == "SpatioTemporalSparseCVI":
+        from .spatio_temporal_variational import SpatioTemporalSparseCVI
+        return SpatioTemporalSparseCVI
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

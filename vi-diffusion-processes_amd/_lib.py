@@ -153,6 +153,8 @@ EXPORTS = {
                               + [ctypes.c_void_p] * 9),
     "mfgm_sparse_pep_sites_q": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_double] * 3
                                 + [ctypes.c_void_p] * 9),
+    "mfgm_st_predict_kl": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_double] * 2 + [ctypes.c_void_p] * 5),
+    "mfgm_st_site_update_q": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
 }
 
 
@@ -187,6 +189,13 @@ class SparseData(ctypes.Structure):
     _fields_ = [("M", ctypes.c_int), ("d", ctypes.c_int), ("N", ctypes.c_int), ("seg", ctypes.c_void_p), ("w", ctypes.c_void_p),
                 ("c", ctypes.c_void_p), ("prior_mean", ctypes.c_void_p), ("prior_cov", ctypes.c_void_p), ("m_lo", ctypes.c_int),
                 ("m_hi", ctypes.c_int)]
+
+
+class StData(ctypes.Structure):
+    """mfgm_st_data (include/mfgm.h)."""
+    _fields_ = [("M", ctypes.c_int), ("Ms", ctypes.c_int), ("dt", ctypes.c_int), ("N", ctypes.c_int), ("seg", ctypes.c_void_p),
+                ("a", ctypes.c_void_p), ("h", ctypes.c_void_p), ("c", ctypes.c_void_p), ("prior_mean", ctypes.c_void_p),
+                ("prior_cov", ctypes.c_void_p)]
 
 
 class KfSites(ctypes.Structure):

@@ -103,7 +103,7 @@ int mfgm_sparse_site_update_q(const mfgm_sparse_data* data, const double* g1, co
     const int ne = (QS + 255) / 256;
 #define SITESQ(NE_) hipLaunchKernelGGL((k_sparse_sites_q<NE_>), grid, dim3(256), shmem, (hipStream_t)stream, sa, g1, g2, lr, nat1, nat2q)
     if (ne <= 1) SITESQ(1); else if (ne <= 2) SITESQ(2); else if (ne <= 3) SITESQ(3); else if (ne <= 4) SITESQ(4);
-    else if (ne <= 8) SITESQ(8); else return 1;
+    else if (ne <= 8) SITESQ(8); else if (ne <= 9) SITESQ(9); else return 1;      // d = 32: QS = 2 080
 #undef SITESQ
     MFGM_CHECK_LAUNCH();
     return 0;

@@ -695,3 +695,79 @@ class Product(_GenericKernel):
                 return None     # a Sum child: not a product of primitive factors
             factors.extend(t[0])
         return [factors] if len(factors) <= 3 else None
+
+
+class IndependentMultiOutput(Sum):
+    """sde_kernel.py:826-880: independent processes stacked into one state, one output per child.  The prior state-space model is that of
+    Sum over the same children (block-diagonal A, Q, Pinf: the packed and the wide construction are inherited); only the emission
+    differs -- block-diagonal [len(kernels), state_dim] where Sum adds the children's rows up."""
+
+    def __init__(self, kernels, jitter=0.0):
+        super().__init__(kernels, jitter)
+        self.output_dim = len(self.kernels)
+
+    def _emission_matrix(self):
+        """[output_dim, state_dim]: row j holds child j's emission row at child j's slice of the state."""
+        H = torch.zeros((len(self.kernels), self.state_dim), dtype=torch.float64)
+        o = 0
+        for j, k in enumerate(self.kernels):
+            H[j, o:o + k.state_dim] = k._emission_row()
+            o += k.state_dim
+        return H
+
+    def generate_emission_model(self, time_points):
+        H = self._emission_matrix().to(time_points.device)
+        return EmissionModel(H.expand(tuple(time_points.shape) + tuple(H.shape)).contiguous(), constant_matrix=H)
+
+
+class SparseSpatioTemporalKernel(IndependentMultiOutput):
+    """spatio_temporal_variational.py:45-106: k((x, t), (x', t')) = k_s(x, x') k_t(t, t') with space marginalised to the Ms inducing
+    locations Z_s -- f(Z_s, .) = chol(K_s(Z_s, Z_s)) [H_t s_1(.), ..., H_t s_Ms(.)] with s_j independent copies of the time kernel's
+    state, state_dim = Ms d_t.  kernel_space: a vidp_amd.space_kernels kernel; jitter is added to K_s(Z_s, Z_s) before its
+    factorisation (0, as in the reference, by default)."""
+
+    def __init__(self, kernel_space, kernel_time, inducing_space, jitter=0.0):
+        inducing_space = torch.as_tensor(inducing_space, dtype=torch.float64)
+        if inducing_space.dim() != 2:
+            raise NotImplementedError("one set of spatial inducing points [Ms, p]; batched inducing points are not supported")
+        if getattr(kernel_time, "output_dim", 1) != 1:
+            raise ValueError("the time kernel must have one output")
+        self.kernel_space, self.kernel_time, self.inducing_space = kernel_space, kernel_time, inducing_space
+        self.space_jitter = float(jitter)
+        super().__init__([kernel_time] * int(inducing_space.shape[0]))
+        self._chol = None
+
+    def _time_emission_row(self, device):
+        """H_t [d_t]; the time kernel's emission must not depend on time."""
+        H = self.kernel_time.generate_emission_model(torch.zeros(1, dtype=torch.float64)).constant_matrix
+        if H is None:
+            raise NotImplementedError("the time kernel's emission matrix must be time-invariant")
+        return H.reshape(-1).to(device, torch.float64)
+
+    def chol_space(self, device=None):
+        """chol(K_s(Z_s, Z_s) + jitter I) [Ms, Ms]."""
+        if self._chol is None:
+            Z = self.inducing_space
+            Kzz = self.kernel_space.K(Z) + self.space_jitter * torch.eye(Z.shape[0], dtype=torch.float64, device=Z.device)
+            self._chol = torch.linalg.cholesky(Kzz)
+        return self._chol if device is None else self._chol.to(device)
+
+    def generate_emission_model(self, time_points):
+        """chol(K_zz) @ blockdiag(H_t) [Ms, Ms d_t], the same at every time point."""
+        dev = time_points.device
+        H = self.chol_space(dev) @ self._emission_matrix().to(dev)
+        return EmissionModel(H.expand(tuple(time_points.shape) + tuple(H.shape)).contiguous(), constant_matrix=H)
+
+    def spatial_features(self, x):
+        """(a [N, Ms], k_s(x, x) - |a|^2 [N]) with a = chol(K_zz)^-1 k_s(Z_s, x): the spatial half of the projection of f(x, t) onto
+        the state and the spatial conditional variance."""
+        L = self.chol_space(x.device)
+        Kzx = self.kernel_space.K(self.inducing_space.to(x.device), x)
+        a = torch.linalg.solve_triangular(L, Kzx, upper=False).transpose(-1, -2).contiguous()
+        return a, self.kernel_space.K_diag(x) - (a * a).sum(-1)
+
+    def state_to_space_conditional_projection(self, inputs):
+        """E[f(x, t) | s(t)] = P s(t): P = k_s(x, Z_s) chol(K_zz)^-T blockdiag(H_t), [N, 1, state_dim]; inputs [N, p + 1], time last."""
+        a, _ = self.spatial_features(inputs[..., :-1])
+        Ht = self._time_emission_row(inputs.device)
+        return (a[..., :, None] * Ht).reshape(tuple(a.shape[:-1]) + (1, self.state_dim))
