@@ -550,6 +550,29 @@ typedef struct mfgm_kernel_terms {
 int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_terms* terms, const double* time_deltas, double* A,
                            double* off, double* chol, int* info, void* stream);
 
+/* A piecewise-stationary kernel (kernels/piecewise_stationary.py `PiecewiseKernel`): nregion - 1 change points c_k cut the time axis
+ * into nregion regions, region r(t) = #{c_k <= t} (a point on a change point belongs to the region after it).  All regions share
+ * base's structure (nterm, nfactor, offset, kind) and jitter; region r has the rates rate[r], variances var[r] (both indexed as
+ * mfgm_kernel_terms' rate / var) and the state mean mean[r].  base's own rate / var / mean are ignored.  The tables are device
+ * arrays; the kernel searches the change points itself. */
+typedef struct mfgm_piecewise_terms {
+    mfgm_kernel_terms base;
+    int nregion;                   /* K + 1 >= 1 */
+    const double* change_points;   /* device [nregion - 1], non-decreasing; may be null when nregion == 1 */
+    const double* rate;            /* device [nregion, 8, 3] */
+    const double* var;             /* device [nregion, 8, 3] */
+    const double* mean;            /* device [nregion, 8]    */
+} mfgm_piecewise_terms;
+
+/* Piecewise kernel -> packed SSM parameters at the time points [B, T] (natural device array, each chain its own sorted grid), the
+ * layout and outputs of mfgm_packed_kernel_ssm.  The transition t_k -> t_k+1 takes the parameters of r = r(t_k), its left end, also
+ * when it crosses a change point: A_k = A_r(t_k+1 - t_k), Q_k = Pinf_r - A_k Pinf_r A_k^T + jitter I by the exact-Q rule of
+ * mfgm_packed_kernel_ssm (an exactly-zero Q stays zero), b_k = (I - A_k) m_r.  Node 0 holds chol(Pinf_r(t_0) + jitter I) and a ZERO
+ * mean (SDEKernel.initial_mean, which PiecewiseKernel inherits).  With nregion == 1 the result is mfgm_packed_kernel_ssm's on the
+ * same terms, apart from the initial mean.  Returns 1 for nregion < 1, a null table, and whatever mfgm_packed_kernel_ssm rejects. */
+int mfgm_packed_piecewise_ssm(const mfgm_plan* plan, const mfgm_piecewise_terms* terms, const double* time_points, double* A,
+                              double* off, double* chol, int* info, void* stream);
+
 /* VDP (markovflow/models/vi_sde.py `VariationalMarkovGP`): drift f_i(x) = af_i x - bf_i x^3, diagonal diffusion q,
  * q(x0) = N(mu0, chol0 chol0^T) (packed lower triangle), grid step dt, learning rate lr. */
 typedef struct mfgm_vdp_params {

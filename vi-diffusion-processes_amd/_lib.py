@@ -63,6 +63,7 @@ EXPORTS = {
     "mfgm_packed_linearize_cubic": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_stationary_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_kernel_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
+    "mfgm_packed_piecewise_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_vdp_workspace_doubles": (ctypes.c_size_t, [ctypes.c_void_p]),
     "mfgm_packed_vdp_to_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_vdp_to_naturals": (ctypes.c_int, [ctypes.c_void_p] * 10),
@@ -215,6 +216,12 @@ class KernelTerms(ctypes.Structure):
     _fields_ = [("nterm", ctypes.c_int), ("nfactor", ctypes.c_int * 8), ("offset", ctypes.c_int * 8), ("kind", (ctypes.c_int * 3) * 8),
                 ("rate", (ctypes.c_double * 3) * 8), ("var", (ctypes.c_double * 3) * 8), ("mean", ctypes.c_double * 8),
                 ("jitter", ctypes.c_double)]
+
+
+class PiecewiseTerms(ctypes.Structure):
+    """mfgm_piecewise_terms (include/mfgm.h)."""
+    _fields_ = [("base", KernelTerms), ("nregion", ctypes.c_int), ("change_points", ctypes.c_void_p), ("rate", ctypes.c_void_p),
+                ("var", ctypes.c_void_p), ("mean", ctypes.c_void_p)]
 
 
 class VdpParams(ctypes.Structure):

@@ -37,8 +37,9 @@ def _conditional_statistics(new_time_points, training_time_points, kernel):
     aug = torch.cat([-inf, training_time_points, inf], dim=-1)
     plus = torch.gather(aug, -1, idx + 1)
     minus = torch.gather(aug, -1, idx)
-    A_mt, Q_mt = kernel.transition_statistics_local(new_time_points - minus)
-    A_tp, Q_tp = kernel.transition_statistics_local(plus - new_time_points)
+    # each transition with the time of its left end, as the reference passes them (a stationary kernel ignores it)
+    A_mt, Q_mt = kernel.transition_statistics_at(minus, new_time_points - minus)
+    A_tp, Q_tp = kernel.transition_statistics_at(new_time_points, plus - new_time_points)
     F, G, T = _conditional_statistics_from_transitions(A_mt, Q_mt, A_tp, Q_tp)
     return torch.cat([F, G], dim=-1), T, idx
 
@@ -76,7 +77,10 @@ def pairwise_marginals(dist, initial_mean, initial_covariance):
     im = initial_mean.to(means.device).expand(means.shape[:-2] + (1, means.shape[-1]))
     ext_m = torch.cat([im, means, im], dim=-2)
     joint_mean = torch.cat([ext_m[..., :-1, :], ext_m[..., 1:, :]], dim=-1)
-    ic = initial_covariance.to(covs.device).expand(covs.shape[:-3] + (1,) + tuple(covs.shape[-2:]))
+    ic = initial_covariance.to(covs.device)
+    if ic.dim() > 2:          # one matrix per chain (a kernel whose initial covariance depends on the first time point)
+        ic = ic.reshape(covs.shape[:-3] + (1,) + tuple(covs.shape[-2:]))
+    ic = ic.expand(covs.shape[:-3] + (1,) + tuple(covs.shape[-2:]))
     ext_c = torch.cat([ic, covs, ic], dim=-3)
     zero = torch.zeros_like(ic)
     ext_s = torch.cat([zero, sub, zero], dim=-3)

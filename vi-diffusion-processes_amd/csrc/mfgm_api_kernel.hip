@@ -1,6 +1,8 @@
-// Sums of products of stationary SDE kernels -> packed SSM parameters (mfgm_kernel_ssm.h).
+// Sums of products of stationary SDE kernels -> packed SSM parameters (mfgm_kernel_ssm.h), one set of parameters for the whole grid
+// or one per region between change points (mfgm_piecewise_ssm.h).
 #include "mfgm_internal.h"
 #include "mfgm_kernel_ssm.h"
+#include "mfgm_piecewise_ssm.h"
 
 using namespace mfgm;
 
@@ -22,17 +24,21 @@ int kernel_ssm_impl(const Plan& P, const KernelTermsDev& kt, const double* dts, 
     MFGM_CHECK_LAUNCH();
     return 0;
 }
-}  // namespace
 
-extern "C" int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_terms* terms, const double* time_deltas, double* A,
-                                      double* off, double* chol, int* info, void* stream) {
-    if (!plan || !terms || !A || !off || !chol || !info) return 1;
-    const Plan& P = plan->p;
+template <int D>
+int piecewise_ssm_impl(const Plan& P, const KernelTermsDev& kt, const PiecewiseDev& pw, const double* tps, double* A, double* off,
+                       double* chol, int* info, hipStream_t st) {
+    const LevelDesc& lv = P.lv[0];
+    hipLaunchKernelGGL((k_piecewise_ssm<D>), dim3(lv.Lpad / 64), dim3(64), 0, st, lv, kt, pw, tps, A, off, chol, info);
+    MFGM_CHECK_LAUNCH();
+    return 0;
+}
+
+// The caller's terms -> the kernels' form (1 x 1 factors behind the others; src[c][slot] = the caller's factor in that slot), with
+// every structural check of the two entry points.  0, or 1 for a structure the kernels do not take.
+int device_terms(const Plan& P, const mfgm_kernel_terms& in, KernelTermsDev& kt, int (*src)[3]) {
     if (P.wide || P.d > 8) return 1;
-    if (P.T > 1 && !time_deltas) return 1;
-    const mfgm_kernel_terms& in = *terms;
     if (in.nterm < 1 || in.nterm > 8) return 1;
-    KernelTermsDev kt;
     memset(&kt, 0, sizeof(kt));
     kt.nterm = in.nterm;
     int dim = 0;
@@ -55,6 +61,7 @@ extern "C" int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_t
                 kt.kind[c][slot] = in.kind[c][f];
                 kt.rate[c][slot] = in.rate[c][f];
                 kt.var[c][slot] = in.var[c][f];
+                src[c][slot] = f;
                 if (fd > 1) shape = shape * 10 + fd;
                 ++slot;
             }
@@ -74,6 +81,38 @@ extern "C" int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_t
     if (dim != P.d) return 1;
     for (int i = 0; i < dim; ++i) kt.mean[i] = in.mean[i];
     kt.jitter = in.jitter;
+    return 0;
+}
+}  // namespace
+
+extern "C" int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_terms* terms, const double* time_deltas, double* A,
+                                      double* off, double* chol, int* info, void* stream) {
+    if (!plan || !terms || !A || !off || !chol || !info) return 1;
+    const Plan& P = plan->p;
+    if (P.T > 1 && !time_deltas) return 1;
+    KernelTermsDev kt;
+    int src[8][3] = {};
+    if (device_terms(P, *terms, kt, src)) return 1;
     hipStream_t st = (hipStream_t)stream;
     MFGM_DISPATCH_D(P.d, (kernel_ssm_impl<DD>(P, kt, time_deltas, A, off, chol, info, st)));
+}
+
+extern "C" int mfgm_packed_piecewise_ssm(const mfgm_plan* plan, const mfgm_piecewise_terms* terms, const double* time_points, double* A,
+                                         double* off, double* chol, int* info, void* stream) {
+    if (!plan || !terms || !time_points || !A || !off || !chol || !info) return 1;
+    const Plan& P = plan->p;
+    const mfgm_piecewise_terms& in = *terms;
+    if (in.nregion < 1 || !in.rate || !in.var || !in.mean) return 1;
+    if (in.nregion > 1 && !in.change_points) return 1;
+    KernelTermsDev kt;
+    PiecewiseDev pw;
+    memset(&pw, 0, sizeof(pw));
+    if (device_terms(P, in.base, kt, pw.src)) return 1;
+    pw.nregion = in.nregion;
+    pw.cp = in.change_points;
+    pw.rate = in.rate;
+    pw.var = in.var;
+    pw.mean = in.mean;
+    hipStream_t st = (hipStream_t)stream;
+    MFGM_DISPATCH_D(P.d, (piecewise_ssm_impl<DD>(P, kt, pw, time_points, A, off, chol, info, st)));
 }

@@ -185,9 +185,19 @@ MFGM_DEV void expand_shape(const TermDesc& td, double dt, bool init, double (&A)
     }
 }
 
-// One transition of length dt: A (full) and Q without jitter (packed lower); init: Q := Pinf and A untouched.
-template <int D>
-MFGM_DEV void terms_transition(const KernelTermsDev& kt, double dt, bool init, double (&A)[D * D], double (&Q)[MFGM_NTRI(D)]) {
+// where a transition's factor parameters come from: the kernel argument (one set for the whole grid) ...
+struct TermParamsArg {
+    const KernelTermsDev& kt;
+    MFGM_DEV double rate(int c, int f) const { return kt.rate[c][f]; }
+    MFGM_DEV double var(int c, int f) const { return kt.var[c][f]; }
+};
+// ... or anything else with rate(c, f) / var(c, f) of term c, slot f (mfgm_piecewise_ssm.h: a lane's row of the region tables)
+
+// One transition of length dt: A (full) and Q without jitter (packed lower); init: Q := Pinf and A untouched.  The structure of the
+// terms is kt's, their rates and variances are prm's.
+template <int D, class Params>
+MFGM_DEV void terms_transition(const KernelTermsDev& kt, const Params& prm, double dt, bool init, double (&A)[D * D],
+                               double (&Q)[MFGM_NTRI(D)]) {
     if (!init) {
 #pragma unroll
         for (int e = 0; e < D * D; ++e) A[e] = 0.0;
@@ -201,8 +211,8 @@ MFGM_DEV void terms_transition(const KernelTermsDev& kt, double dt, bool init, d
 #pragma unroll
         for (int f = 0; f < 3; ++f) {
             td.kind[f] = kt.kind[c][f];
-            td.rate[f] = kt.rate[c][f];
-            td.var[f] = kt.var[c][f];
+            td.rate[f] = prm.rate(c, f);
+            td.var[f] = prm.var(c, f);
             td.nx += factor_exact(td.kind[f]) ? 0 : 1;
         }
         switch (kt.shape[c]) {
@@ -237,7 +247,7 @@ static __global__ __launch_bounds__(64) void k_kernel_ssm(LevelDesc lv, KernelTe
         const bool init = (t < 0);
         const bool has = (t + 1 < n);
         if (has) {
-            terms_transition<D>(kt, init ? 0.0 : dtb[t], init, A, Q);
+            terms_transition<D>(kt, TermParamsArg{kt}, init ? 0.0 : dtb[t], init, A, Q);
         } else {
 #pragma unroll
             for (int e = 0; e < EF; ++e) A[e] = 0.0;

@@ -9,6 +9,7 @@ Seasonal priors (markovflow/kernels/periodic.py `HarmonicOscillator`, kernels/co
 state_dim <= 8 and through the torch closed forms otherwise.
 """
 import math
+import os
 
 import torch
 
@@ -227,6 +228,15 @@ class StationaryKernel:
     def initial_covariance_matrix(self):
         """Pinf + jitter (sde_kernel.py:402-419)."""
         return self.steady_state_covariance + self.jitter * torch.eye(self.state_dim, dtype=torch.float64)
+
+    # -- the time-aware forms the models call (SDEKernel.initial_covariance / transition_statistics take the time of the state or of the
+    #    transition's left end, sde_kernel.py:113-151): a stationary kernel ignores the times --------------------------------------------
+    def initial_covariance(self, initial_time_point=None):
+        return self.initial_covariance_matrix()
+
+    def transition_statistics_at(self, transition_times, time_deltas):
+        """(A, Q) of the transitions that start at transition_times and last time_deltas (any shape, unordered)."""
+        return self.transition_statistics_local(time_deltas)
 
     def generate_emission_model(self, time_points):
         """H = [1, 0, ...] per component, tiled over the time points (sde_kernel.py:173-211, 670-687)."""
@@ -771,3 +781,232 @@ class SparseSpatioTemporalKernel(IndependentMultiOutput):
         a, _ = self.spatial_features(inputs[..., :-1])
         Ht = self._time_emission_row(inputs.device)
         return (a[..., :, None] * Ht).reshape(tuple(a.shape[:-1]) + (1, self.state_dim))
+
+
+class PiecewiseKernel:
+    """kernels/piecewise_stationary.py:28-289: an SDE kernel whose dynamics are those of kernels[r] on the r-th of the K + 1 regions the
+    K sorted change points c_0 <= ... <= c_{K-1} cut the time axis into, r(t) = #{c_k <= t} (a point on a change point belongs to the
+    region after it).  The children are of one class and differ only in their parameter values (lengthscales / rates, variances, state
+    means); they may be Sum / Product trees.
+
+    The transition t_k -> t_k+1 of a state-space model is governed by the region of its LEFT end: A_k = A_r(t_k+1 - t_k),
+    Q_k = Pinf_r - A_k Pinf_r A_k^T + jitter, b_k = (I - A_k) m_r with r = r(t_k).  As in the reference, state-space models built by
+    marginalising the process to time points are only valid if no transitions cross a change point: put the change points on time
+    points of the grid (two grids that cut a region differently around a change point otherwise define different priors).
+
+    The first state has covariance Pinf_r(t_0) + jitter and mean ZERO: the reference's PiecewiseKernel inherits
+    SDEKernel.initial_mean, which returns zeros whatever the children's state means are.
+
+    state_dim <= 8 and a tree mfgm_kernel_terms expresses: state_space_model is one launch of mfgm_packed_piecewise_ssm (the kernel
+    looks the regions up itself); otherwise the torch closed forms of the children, selected by region, and the wide sweeps."""
+
+    def __init__(self, kernels, change_points, output_dim=1, jitter=0.0):
+        kernels = list(kernels)
+        if not kernels:
+            raise ValueError("There must be at least one child kernel.")
+        if not all(isinstance(k, StationaryKernel) for k in kernels):
+            raise TypeError("can only combine Kernel instances")
+        if not all(type(k) is type(kernels[0]) for k in kernels):
+            raise TypeError("can only combine kernels from the same class")
+        if output_dim != 1 or any(k.output_dim != 1 for k in kernels):
+            raise ValueError("only output_dim == 1 kernels are on the hot path")
+        cp = torch.as_tensor(change_points, dtype=torch.float64).detach().reshape(-1).cpu()
+        if len(kernels) != cp.numel() + 1:
+            raise ValueError(f"{cp.numel()} change points need {cp.numel() + 1} kernels, got {len(kernels)}")
+        if cp.numel() > 1 and bool((cp[1:] < cp[:-1]).any()):
+            raise ValueError("the change points must be sorted")
+        if any(_tree_jitter(k) for k in kernels):
+            raise ValueError("a jitter on a child of PiecewiseKernel is not supported; set it on the PiecewiseKernel")
+        structs = [_structure(k) for k in kernels]
+        if any(st != structs[0] for st in structs[1:]):
+            raise ValueError("the children of PiecewiseKernel must have the same structure (they may differ in parameter values only)")
+        self.kernels, self.change_points = kernels, cp
+        self.num_change_points = int(cp.numel())
+        self.output_dim, self.jitter = 1, float(jitter)
+        self._state_dim = kernels[0].state_dim
+
+    @property
+    def state_dim(self):
+        return self._state_dim
+
+    # -- regions ------------------------------------------------------------------------------------------------------------------------
+    def split_time_indices(self, time_points):
+        """Index 0 .. K of the region every time point lies in (any shape): #{c_k <= t}, i.e. searchsorted(..., "right") - 1 on the
+        change points augmented with -inf and +inf (piecewise_stationary.py:126-143)."""
+        t = torch.as_tensor(time_points, dtype=torch.float64)
+        return torch.searchsorted(self.change_points.to(t.device), t.contiguous(), right=True)
+
+    def _by_region(self, per_child, time_points):
+        table = torch.stack([torch.as_tensor(x, dtype=torch.float64) for x in per_child])
+        r = self.split_time_indices(time_points)
+        return table.to(r.device)[r]
+
+    def steady_state_covariances(self, time_points):
+        """Pinf of the kernel active at each time point, [..., d, d]."""
+        return self._by_region([k.steady_state_covariance for k in self.kernels], time_points)
+
+    def feedback_matrices(self, time_points):
+        """F of the kernel active at each time point, [..., d, d]."""
+        return self._by_region([k.feedback_matrix for k in self.kernels], time_points)
+
+    def state_means(self, time_points):
+        """State mean of the kernel active at each time point, [..., d]."""
+        return self._by_region([k.state_mean for k in self.kernels], time_points)
+
+    # -- transitions: torch closed forms of the children, selected by the region of the transition's left end ---------------------------
+    def transition_statistics_at(self, transition_times, time_deltas):
+        """(A, Q) of the transitions that start at transition_times and last time_deltas (any shape, unordered): every child's closed
+        forms on all gaps, then a selection by region (no host synchronisation, K + 1 times the arithmetic)."""
+        r = self.split_time_indices(transition_times)[..., None, None]
+        A = Q = None
+        for i, k in enumerate(self.kernels):
+            Ai, Qi = k.transition_statistics_local(time_deltas)
+            A, Q = (Ai, Qi) if A is None else (torch.where(r == i, Ai, A), torch.where(r == i, Qi, Q))
+        return A, Q + self.jitter * torch.eye(self.state_dim, dtype=Q.dtype, device=Q.device)
+
+    def transition_statistics(self, transition_times, time_deltas):
+        """piecewise_stationary.py:206-228.  Only valid if no transition crosses a change point."""
+        return self.transition_statistics_at(transition_times, time_deltas)
+
+    def state_transitions(self, transition_times, time_deltas):
+        """piecewise_stationary.py:180-204.  Only valid if no transition crosses a change point."""
+        return self.transition_statistics_at(transition_times, time_deltas)[0]
+
+    def state_offsets(self, transition_times, time_deltas):
+        """b = (I - A) m of the region of the transition's left end (piecewise_stationary.py:248-271)."""
+        A = self.state_transitions(transition_times, time_deltas)
+        m = self.state_means(transition_times).to(A.device)
+        return m - (A @ m[..., None])[..., 0]
+
+    def initial_covariance(self, initial_time_point):
+        """Pinf + jitter of the kernel active at the time of the first state: [d, d] for one time ([1] or a scalar), batch_shape + [d, d]
+        for batch_shape + [1] (piecewise_stationary.py:111-124)."""
+        t = torch.as_tensor(initial_time_point, dtype=torch.float64)
+        P = self.steady_state_covariances(t) + self.jitter * torch.eye(self.state_dim, dtype=torch.float64, device=t.device)
+        return P[..., 0, :, :] if t.dim() >= 1 else P
+
+    def initial_mean(self, batch_shape=()):
+        """Zeros, as in the reference (SDEKernel.initial_mean; the children's state means enter the offsets only)."""
+        return torch.zeros(tuple(batch_shape) + (self.state_dim,), dtype=torch.float64)
+
+    def _emission_row(self):
+        return self.kernels[0]._emission_row()
+
+    def generate_emission_model(self, time_points):
+        """The children's common H, the same at every time point."""
+        h = self._emission_row().to(time_points.device)[None]
+        return EmissionModel(h.expand(tuple(time_points.shape) + (1, self.state_dim)).contiguous(), constant_matrix=h)
+
+    # -- the prior state-space model ----------------------------------------------------------------------------------------------------
+    def _terms(self):
+        terms = [k._terms() for k in self.kernels] if self.state_dim <= 8 else None
+        return None if terms is None or terms[0] is None or len(terms[0]) > 8 else terms
+
+    def _terms_struct(self, device):
+        """(mfgm_piecewise_terms, the device tensor that holds its tables): one host-to-device copy."""
+        terms = self._terms()
+        if terms is None:
+            raise ValueError("the piecewise kernel takes up to 8 terms of up to 3 primitive factors and state_dim <= 8")
+        K1, d = len(self.kernels), self.state_dim
+        pw = _lib.PiecewiseTerms()
+        base = self.kernels[0]._terms_struct(terms[0])
+        base.jitter = self.jitter
+        pw.base, pw.nregion = base, K1
+        rate, var = torch.zeros((K1, 8, 3), dtype=torch.float64), torch.zeros((K1, 8, 3), dtype=torch.float64)
+        mean = torch.zeros((K1, 8), dtype=torch.float64)
+        for r, (k, tr) in enumerate(zip(self.kernels, terms)):
+            for c, factors in enumerate(tr):
+                for f, (_, ra, va) in enumerate(factors):
+                    rate[r, c, f], var[r, c, f] = ra, va
+            mean[r, :d] = k.state_mean
+        host = torch.cat([rate.reshape(-1), var.reshape(-1), mean.reshape(-1), self.change_points])
+        tab = host.to(device)
+        n = K1 * 24
+        pw.rate, pw.var, pw.mean = tab.data_ptr(), tab[n:].data_ptr(), tab[2 * n:].data_ptr()
+        pw.change_points = tab[2 * n + K1 * 8:].data_ptr() if K1 > 1 else None
+        return pw, tab
+
+    # VIDP_PIECEWISE_TORCH=1: the region-selected torch closed forms also where the HIP kernel applies (the tests compare the two routes)
+    def state_space_model(self, time_points, plan=None):
+        """Prior SSM at the sorted time points [..., T], each chain with its own grid.  Only valid if no transition crosses a change
+        point (a crossing transition is governed by its left end)."""
+        t, bs = _flat(time_points, 1)
+        B, T = t.shape
+        if plan is None:
+            plan = Plan(B, T, self.state_dim, device=t.device)
+        if self._terms() is None or os.environ.get("VIDP_PIECEWISE_TORCH", "0") == "1":
+            return self._state_space_model_torch(t, bs, plan)
+        pw, tab = self._terms_struct(t.device)
+        A, off, chol = plan.piecewise_ssm(pw, t)
+        try:
+            plan.check_info()
+        except ArithmeticError as e:
+            raise ArithmeticError(_NOT_PD) from e
+        ssm = _ssm_from_packed(plan, A, off, chol)
+        ssm.batch_shape = bs
+        ssm._piecewise_tables = tab      # the launch reads them: kept with the model
+        return ssm
+
+    def _state_space_model_torch(self, t, bs, plan):
+        """The steps of StationaryKernel._state_space_model_wide on the region-selected closed forms."""
+        dev, d = t.device, self.state_dim
+        A, Q = self.transition_statistics_at(t[:, :-1], t[:, 1:] - t[:, :-1])
+        zero = (Q == 0).all(dim=-1).all(dim=-1)
+        eye = torch.eye(d, dtype=Q.dtype, device=dev)
+        try:
+            chol = linalg.cholesky(torch.where(zero[..., None, None], eye, Q))
+            chol0 = linalg.cholesky(self.initial_covariance(t[:, :1]))
+        except ArithmeticError as e:
+            raise ArithmeticError(_NOT_PD) from e
+        chol = torch.where(zero[..., None, None], torch.zeros_like(chol), chol)
+        m = self.state_means(t[:, :-1])
+        off = m - (A @ m[..., None])[..., 0]
+        ssm = StateSpaceModel(torch.zeros((t.shape[0], d), dtype=torch.float64, device=dev), chol0.contiguous(), A, off, chol, plan=plan)
+        ssm.batch_shape = bs
+        return ssm
+
+    # -- hyper-parameters as leaves of a torch graph ------------------------------------------------------------------------------------
+    def hyperparameter_leaves(self, device="cpu"):
+        """One entry per region: the children's hyperparameter_leaves."""
+        return [k.hyperparameter_leaves(device) for k in self.kernels]
+
+    def differentiable_ssm(self, time_points, leaves=None, plan=None):
+        """(tape.TapeSSM, leaves): the prior SSM at the sorted time points [T] (one chain, d <= 8) as a differentiable function of the
+        per-region hyper-parameter leaves -- the children's differentiable _parts on all gaps, selected by the region of each
+        transition's left end; a region that holds no left end and not the first point gets a gradient of exactly zero."""
+        from . import tape
+        t = time_points.reshape(-1)
+        dev, d = t.device, self.state_dim
+        if leaves is None:
+            leaves = self.hyperparameter_leaves(dev)
+        r = self.split_time_indices(t)
+        rl, dt = r[:-1, None, None], t[1:] - t[:-1]
+        A = Qt = Pinf0 = None
+        exact = True
+        for i, (k, lv) in enumerate(zip(self.kernels, leaves)):
+            Ai, Pi, Qi, ex = k._parts(dt, lv)
+            exact = exact and ex
+            Pi = Pi.expand(d, d)
+            A, Qt = (Ai, Qi) if A is None else (torch.where(rl == i, Ai, A), torch.where(rl == i, Qi, Qt))
+            Pinf0 = Pi if Pinf0 is None else torch.where(r[0] == i, Pi, Pinf0)
+        jit = self.jitter * torch.eye(d, dtype=torch.float64, device=dev)
+        Q = Qt + jit
+        m = self.state_means(t[:-1])
+        b = m - (A @ m[..., None])[..., 0]
+        cq = torch.zeros_like(Q) if (exact and self.jitter == 0.0) else tape.cholesky(0.5 * (Q + Q.transpose(-1, -2)))
+        mu0 = torch.zeros((1, d), dtype=torch.float64, device=dev)
+        return tape.TapeSSM(mu0, tape.cholesky(Pinf0 + jit)[None], A[None], b[None], cq[None], plan=plan), leaves
+
+
+def _tree_jitter(kernel):
+    """Whether the kernel or any kernel below it carries a jitter."""
+    return kernel.jitter != 0.0 or any(_tree_jitter(k) for k in getattr(kernel, "kernels", []))
+
+
+def _structure(kernel):
+    """What the children of a PiecewiseKernel must share: the class tree, the state dimension, the emission row and, where the tree
+    has them, the kinds of the terms' factors -- everything of _terms() but the rates and variances."""
+    terms = kernel._terms() if kernel.state_dim <= 8 else None
+    kinds = None if terms is None else [[kind for kind, _, _ in factors] for factors in terms]
+    tree = lambda k: (type(k).__name__, [tree(c) for c in getattr(k, "kernels", [])])
+    return tree(kernel), kernel.state_dim, kernel._emission_row().tolist(), kinds

@@ -319,6 +319,17 @@ class Plan:
                                                    _ptr(self.info), _stream()), "mfgm_packed_kernel_ssm")
         return A, off, chol
 
+    def piecewise_ssm(self, pw, time_points):
+        """Piecewise-stationary kernel (_lib.PiecewiseTerms, its tables on the device) -> packed SSM parameters (A, off, chol);
+        time_points natural [B, T], one sorted grid per chain."""
+        A, off, chol = self.empty(FULL), self.empty(VEC), self.empty(TRI)
+        tp = time_points.contiguous()
+        if tuple(tp.shape) != (self.B, self.T):
+            raise ValueError(f"time_points has shape {tuple(tp.shape)}, expected {(self.B, self.T)}")
+        _lib.check(self.lib.mfgm_packed_piecewise_ssm(self.h, ctypes.byref(pw), _ptr(tp), _ptr(A), _ptr(off), _ptr(chol),
+                                                      _ptr(self.info), _stream()), "mfgm_packed_piecewise_ssm")
+        return A, off, chol
+
     def node_ids(self, time_index):
         """int64 device tensor b*T + t for every chain and every index in `time_index` ([n] or [B, n])."""
         ti = torch.as_tensor(time_index, dtype=torch.int64, device=self.device)

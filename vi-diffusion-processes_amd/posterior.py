@@ -22,7 +22,8 @@ class ConditionalProcess:
         if (new_time_points.dim() == 1 and self.conditioning_time_points.dim() == 1 and tuple(q.batch_shape) == () and new_time_points.is_cuda
                 and q.d <= 32 and os.environ.get("VIDP_FUSED_PREDICT", "1") != "0"):
             return self._predict_state_fused(new_time_points)
-        pw_mu, pw_cov = pairwise_marginals(q, self.kernel.initial_mean(q.batch_shape), self.kernel.initial_covariance_matrix())
+        pw_mu, pw_cov = pairwise_marginals(q, self.kernel.initial_mean(q.batch_shape),
+                                            self.kernel.initial_covariance(self.conditioning_time_points[..., :1]))
         return conditional_predict(new_time_points, self.conditioning_time_points, self.kernel, pw_mu, pw_cov)
 
     def _predict_state_fused(self, new_time_points):
@@ -45,7 +46,7 @@ class ConditionalProcess:
         N = int(new_time_points.shape[0])
         dev = new_time_points.device
         pm = self.kernel.initial_mean(()).to(dev, torch.float64).contiguous()
-        pc = self.kernel.initial_covariance_matrix().to(dev, torch.float64).contiguous()
+        pc = self.kernel.initial_covariance(self.conditioning_time_points[:1]).to(dev, torch.float64).contiguous()
         mean = torch.empty((N, d), dtype=torch.float64, device=dev)
         cov = torch.empty((N, d, d), dtype=torch.float64, device=dev)
         idx32 = idx.to(torch.int32).contiguous()

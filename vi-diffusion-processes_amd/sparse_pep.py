@@ -120,6 +120,10 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
             raise NotImplementedError("SparsePowerExpectationPropagation runs one chain: inducing points [M]")
         if inducing_points.shape[0] < 2:
             raise ValueError("at least two inducing points are needed")
+        from .kernels import PiecewiseKernel
+        if isinstance(kernel, PiecewiseKernel):
+            raise NotImplementedError("SparsePowerExpectationPropagation does not take a PiecewiseKernel: its pair priors assume one "
+                                      "stationary kernel on the whole axis")
         # the parent's objectives (classic_elbo, predict_log_density) take variational expectations: they get the wrapped likelihood
         base = likelihood if hasattr(likelihood, "variational_expectations") else likelihood.base
         super().__init__(kernel, inducing_points, base, mean_function, float(learning_rate))

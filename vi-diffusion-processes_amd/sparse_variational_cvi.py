@@ -184,7 +184,7 @@ class SparseCVIGaussianProcess:
             seg = torch.zeros(m_hi - m_lo + 1, dtype=torch.int32, device=z.device)
             seg[1:] = torch.cumsum(torch.bincount(idx - m_lo, minlength=m_hi - m_lo), 0).to(torch.int32)
             pm = self._kernel.initial_mean(()).to(z.device, torch.float64).contiguous()
-            pc = self._kernel.initial_covariance_matrix().to(z.device, torch.float64).contiguous()
+            pc = self._kernel.initial_covariance(z[:1]).to(z.device, torch.float64).contiguous()
             sd = _lib.SparseData()
             sd.M, sd.d, sd.N, sd.m_lo, sd.m_hi = M, d, N, m_lo, m_hi
             sd.seg, sd.w, sd.c, sd.prior_mean, sd.prior_cov = seg.data_ptr(), w.data_ptr(), cc.data_ptr(), pm.data_ptr(), pc.data_ptr()

@@ -45,6 +45,10 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
             raise NotImplementedError("one chain: inducing_time [M_t] and inducing_space [Ms, p]; batched inducing points are not supported")
         if mean_function is not None and not callable(mean_function):
             raise ValueError("mean_function must be a callable X -> [N, 1]")
+        from .kernels import PiecewiseKernel
+        if isinstance(kernel_time, PiecewiseKernel):
+            raise NotImplementedError("SpatioTemporalSparseCVI does not take a PiecewiseKernel as its time kernel: the stacked state is a "
+                                      "Sum of stationary kernels")
         inducing_space = torch.as_tensor(inducing_space, dtype=torch.float64).to(inducing_time.device)
         Ms, d_t = int(inducing_space.shape[0]), int(kernel_time.state_dim)
         if Ms * d_t > MAX_STATE_DIM:
