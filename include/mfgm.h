@@ -573,6 +573,32 @@ typedef struct mfgm_piecewise_terms {
 int mfgm_packed_piecewise_ssm(const mfgm_plan* plan, const mfgm_piecewise_terms* terms, const double* time_points, double* A,
                               double* off, double* chol, int* info, void* stream);
 
+/* A latent exponentially generated kernel (kernels/latent_exp_generated.py:79-142 `LatentExponentiallyGenerated`, the LEG-GP of
+ * Loper et al. 2020): dx = -1/2 G x dt + N dw with G = N N^T + R - R^T for arbitrary N, R [d, d], hence Pinf = I.  The caller
+ * forms the feedback matrix F = -1/2 G; d <= 8. */
+typedef struct mfgm_leg_spec {
+    int d;
+    double F[64];       /* row-major, d x d used (row stride d) */
+    double mean[8];
+    double jitter;
+} mfgm_leg_spec;
+
+/* LEG kernel -> packed SSM parameters on a time grid (SDEKernel.state_space_model, sde_kernel.py:153-171, on
+ * latent_exp_generated.py:79-142), the layout, outputs and *info convention of mfgm_packed_kernel_ssm; time_deltas natural
+ * [B, T-1].  A_k = expm(F dt_k) by scaling and squaring on a Taylor polynomial (scaled so that |F|_1 dt / 2^s <= 1/2, degree chosen so
+ * that the first dropped term is below 1e-18), Q_k = I - A_k A_k^T + jitter I, Cholesky factored (dt_k = 0 gives A_k = I and Q_k = 0
+ * exactly, and an exactly-zero Q stays zero; a Q neither positive definite nor zero sets *info), b_k = (I - A_k) m; node 0 holds
+ * (m, chol((1 + jitter) I)).  The result of a transition depends on its gap only: equal gaps give bit-identical blocks.  Returns 1,
+ * before any HIP call, for a null spec or pointer, d < 1, d > 8, or a plan of another state dimension. */
+int mfgm_packed_leg_ssm(const mfgm_plan* plan, const mfgm_leg_spec* spec, const double* time_deltas, double* A, double* off,
+                        double* chol, int* info, void* stream);
+
+/* (A, Q) of the LEG kernel for n arbitrary non-negative gaps, unordered (StationaryKernel.transition_statistics, sde_kernel.py:421-446,
+ * on latent_exp_generated.py:79-142): time_deltas [n], A [n, d, d] = expm(F dt), Q [n, d, d] = I - A A^T + jitter I (symmetric, not
+ * factored), natural device arrays; the exponential of mfgm_packed_leg_ssm, so the two agree bit for bit in A.  Returns 1, before
+ * any HIP call, for a null spec or pointer, d < 1, d > 8 or n < 0; n == 0 returns 0 without a launch. */
+int mfgm_leg_transitions(const mfgm_leg_spec* spec, long n, const double* time_deltas, double* A, double* Q, void* stream);
+
 /* VDP (markovflow/models/vi_sde.py `VariationalMarkovGP`): drift f_i(x) = af_i x - bf_i x^3, diagonal diffusion q,
  * q(x0) = N(mu0, chol0 chol0^T) (packed lower triangle), grid step dt, learning rate lr. */
 typedef struct mfgm_vdp_params {

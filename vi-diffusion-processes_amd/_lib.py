@@ -64,6 +64,8 @@ EXPORTS = {
     "mfgm_packed_stationary_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_kernel_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_piecewise_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
+    "mfgm_packed_leg_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
+    "mfgm_leg_transitions": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long] + [ctypes.c_void_p] * 4),
     "mfgm_vdp_workspace_doubles": (ctypes.c_size_t, [ctypes.c_void_p]),
     "mfgm_packed_vdp_to_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_vdp_to_naturals": (ctypes.c_int, [ctypes.c_void_p] * 10),
@@ -222,6 +224,11 @@ class PiecewiseTerms(ctypes.Structure):
     """mfgm_piecewise_terms (include/mfgm.h)."""
     _fields_ = [("base", KernelTerms), ("nregion", ctypes.c_int), ("change_points", ctypes.c_void_p), ("rate", ctypes.c_void_p),
                 ("var", ctypes.c_void_p), ("mean", ctypes.c_void_p)]
+
+
+class LegSpec(ctypes.Structure):
+    """mfgm_leg_spec (include/mfgm.h)."""
+    _fields_ = [("d", ctypes.c_int), ("F", ctypes.c_double * 64), ("mean", ctypes.c_double * 8), ("jitter", ctypes.c_double)]
 
 
 class VdpParams(ctypes.Structure):

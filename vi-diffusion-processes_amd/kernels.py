@@ -7,7 +7,11 @@ Cholesky factors in one HIP kernel (k_stationary_ssm) directly in the packed lay
 Seasonal priors (markovflow/kernels/periodic.py `HarmonicOscillator`, kernels/constant.py `Constant`, kernels/sde_kernel.py
 `Product`) and any Sum / Product tree holding them go through the generic term kernel k_kernel_ssm (mfgm_packed_kernel_ssm) for
 state_dim <= 8 and through the torch closed forms otherwise.
+
+Learnable dynamics (markovflow/kernels/latent_exp_generated.py `LatentExponentiallyGenerated`) have no closed-form transition: the
+matrix exponentials of every transition are evaluated by k_leg_ssm (mfgm_packed_leg_ssm).
 """
+import ctypes
 import math
 import os
 
@@ -637,6 +641,116 @@ class Constant(_GenericKernel):
 
     def _terms(self):
         return [[(_lib.FACTOR_CONSTANT, 0.0, self.variance)]]
+
+
+class LatentExponentiallyGenerated(_GenericKernel):
+    """kernels/latent_exp_generated.py:28-142, the LEG-GP kernel of Loper et al. (2020): dx = -1/2 G x dt + N dw with
+    G = N N^T + R - R^T for arbitrary N (noise mixing) and R (rotation inducing) [d, d], so feedback_matrix F = -G / 2,
+    steady_state_covariance = I, A(dt) = expm(F dt) and Q(dt) = I - A A^T.  The only kernel of the family whose dynamics are free
+    parameters, and the only one without a closed-form transition.
+
+    Emission: the reference sets output_dim = state_dim with every emission row e_1.  This package is single-output, so here
+    output_dim = 1 and the emission row is e_1 by default, which fixes k(0) = 1; `emission` [d] supplies the LEG paper's B instead,
+    k(tau) = B expm(F |tau|) B^T.  The emission is not trainable.
+
+    state_dim <= 8 on the device: state_space_model is one launch of mfgm_packed_leg_ssm (scaling-and-squaring Taylor exponential, Q,
+    chol Q and the offsets of every transition, DESIGN.md section 17) and transition_statistics_local one of mfgm_leg_transitions;
+    for state_dim > 8 or CPU tensors torch.linalg.matrix_exp (and, on the device, the wide sweeps).  _state_space_model_wide calls
+    transition_statistics_local, so on the device with state_dim <= 8 it too takes the HIP transitions; _generic_local is the torch
+    route at any size.  Hyper-parameter gradients go through matrix_exp's backward and the tape.
+    Inside Sum / Product / PiecewiseKernel a LEG child takes the torch routes (_terms() is None)."""
+
+    def __init__(self, N, R, jitter=0.0, emission=None):
+        N = torch.as_tensor(N, dtype=torch.float64).detach().cpu()
+        R = torch.as_tensor(R, dtype=torch.float64).detach().cpu()
+        if N.dim() != 2 or N.shape[0] != N.shape[1] or N.shape[0] < 1 or tuple(R.shape) != tuple(N.shape):
+            raise ValueError(f"N and R must be square matrices of one shape, got {tuple(N.shape)} and {tuple(R.shape)}")
+        super().__init__(1, jitter)
+        self.N, self.R = N.clone(), R.clone()
+        self.state_dim = int(N.shape[0])
+        if emission is not None:
+            emission = torch.as_tensor(emission, dtype=torch.float64).detach().cpu().reshape(-1).clone()
+            if emission.numel() != self.state_dim:
+                raise ValueError(f"emission must have {self.state_dim} entries, got {emission.numel()}")
+        self.emission = emission
+
+    @staticmethod
+    def _feedback(N, R):
+        return -0.5 * (N @ N.transpose(-1, -2) + R - R.transpose(-1, -2))
+
+    @property
+    def feedback_matrix(self):
+        return self._feedback(self.N, self.R)
+
+    @property
+    def steady_state_covariance(self):
+        return torch.eye(self.state_dim, dtype=torch.float64)
+
+    def hyperparameter_leaves(self, device="cpu"):
+        mk = lambda v: v.clone().to(device).requires_grad_(True)
+        return {"N": mk(self.N), "R": mk(self.R)}
+
+    def _parts(self, dt, leaves=None):
+        F = self.feedback_matrix.to(dt.device) if leaves is None else self._feedback(leaves["N"], leaves["R"])
+        A = torch.linalg.matrix_exp(F * dt[..., None, None])
+        eye = torch.eye(self.state_dim, dtype=torch.float64, device=dt.device)
+        return A, eye, eye - A @ A.transpose(-1, -2), False
+
+    def _emission_row(self):
+        if self.emission is not None:
+            return self.emission.clone()
+        return super()._emission_row()
+
+    def _terms(self):
+        return None
+
+    def _spec(self):
+        """mfgm_leg_spec of this kernel: F formed here, in fp64."""
+        d = self.state_dim
+        if d > 8:
+            raise ValueError("the LEG kernels take state_dim <= 8")
+        spec = _lib.LegSpec()
+        spec.d = d
+        F, m = self.feedback_matrix.reshape(-1).tolist(), self.state_mean.tolist()
+        for e in range(d * d):
+            spec.F[e] = F[e]
+        for i in range(d):
+            spec.mean[i] = m[i]
+        spec.jitter = self.jitter
+        return spec
+
+    def state_space_model(self, time_points, plan=None):
+        t, bs = _flat(time_points, 1)
+        if self.state_dim > 8 or not t.is_cuda:
+            return self._generic_ssm(time_points, plan)
+        B, T = t.shape
+        if plan is None:
+            plan = Plan(B, T, self.state_dim, device=t.device)
+        A, off, chol = plan.leg_ssm(self._spec(), (t[:, 1:] - t[:, :-1]).contiguous())
+        try:
+            plan.check_info()
+        except ArithmeticError as e:
+            raise ArithmeticError(_NOT_PD) from e
+        ssm = _ssm_from_packed(plan, A, off, chol)
+        ssm.batch_shape = bs
+        return ssm
+
+    def transition_statistics_local(self, time_deltas):
+        """(A, Q) for arbitrary, unordered time gaps (any shape): one launch of mfgm_leg_transitions on the device for state_dim <= 8,
+        torch.linalg.matrix_exp otherwise."""
+        if self.state_dim > 8 or not time_deltas.is_cuda:
+            return self._generic_local(time_deltas)
+        from .packed import _ptr, _stream
+        d = self.state_dim
+        td = time_deltas.detach().to(torch.float64).contiguous()
+        A = torch.empty(tuple(td.shape) + (d, d), dtype=torch.float64, device=td.device)
+        Q = torch.empty_like(A)
+        if td.numel():
+            spec = self._spec()
+            with torch.cuda.device(td.device):
+                _lib.check(_lib.load().mfgm_leg_transitions(ctypes.byref(spec), td.numel(), _ptr(td), _ptr(A), _ptr(Q), _stream()),
+                           "mfgm_leg_transitions")
+        return A, Q
 
 
 class Product(_GenericKernel):
