@@ -215,23 +215,28 @@ def test_sde_kl_kernel(amd, rng, d, kind):
         assert_close(gsub[b], os_)
 
 
-@pytest.mark.parametrize("d,kind,B,T", [(1, "ou", 1, 60), (1, "dw", 2, 50), (2, "dw", 2, 45), (6, "dw", 2, 150), (6, "ou", 3, 67)])
+@pytest.mark.parametrize("d,kind,B,T", [(1, "ou", 1, 60), (1, "dw", 2, 50), (2, "dw", 2, 45), (6, "dw", 2, 150), (6, "ou", 3, 67),
+                                        (4, "dw", 2, 70), (5, "ou", 2, 61), (7, "dw", 1, 50), (8, "ou", 2, 45), (3, "dw+ends", 2, 41)])
 def test_cvi_sites_sde(amd, rng, d, kind, B, T):
     """CVISitesSDE (CVI-DP): linearised prior, data-site and Girsanov updates, ELBO, re-linearisation, per trajectory.
     d = 6 is the bench's state dimension (ragged partition: T is not a multiple of the segment length); there the oracle takes
     its expectations from the cubic's Gaussian moments (closed_form, pinned to the reference's quadrature route at d <= 2 in
-    tests/test_oracle_models.py -- the 20^6-point grid itself is out of reach)."""
+    tests/test_oracle_models.py -- the 20^6-point grid itself is out of reach).  "+ends": the first and the last node of the chain
+    are observed (node 0 is where the data site and P0^{-1} meet in one block)."""
     import torch
     from oracle import np_sde
     from vidp_amd import sde as gsde
     from vidp_amd.likelihoods import MultivariateGaussian
     from vidp_amd.variational_cvi_sde import CVISitesSDE
+    kind, _, ends = kind.partition("+")
     dt = 0.02
     qd = np.ones(d)
     osde = np_sde.OrnsteinUhlenbeckSDE(1.2, np.diag(qd)) if kind == "ou" else np_sde.DoubleWellSDE(np.diag(qd))
     gs = gsde.OrnsteinUhlenbeckSDE(1.2, torch.from_numpy(np.diag(qd))) if kind == "ou" else gsde.DoubleWellSDE(torch.from_numpy(np.diag(qd)))
     grid = np.arange(T) * dt
     idx = np.sort(rng.choice(np.arange(1, T), size=6, replace=False))
+    if ends:
+        idx[0], idx[-1] = 0, T - 1
     y = np.sign(rng.normal(size=(B, 6, d))) + 0.2 * rng.normal(size=(B, 6, d))
     cholR = 0.3 * np.eye(d) + (0.1 * np.eye(d, k=-1) if d > 2 else 0.0)     # d = 6: full d x d data sites, as in the bench
     init = (np.zeros(d), 0.5 * np.eye(d))
@@ -1247,7 +1252,8 @@ def test_variational_markov_gp_stabilized(amd, rng):
     assert ssm_A <= 1.0 + 1e-12
 
 
-@pytest.mark.parametrize("d,kind,B,T,R0", [(1, "dw", 3, 57, 8), (2, "dw", 2, 61, 8), (3, "ou", 2, 64, 4), (6, "dw", 3, 131, 8), (6, "dw", 1, 33, 16)])
+@pytest.mark.parametrize("d,kind,B,T,R0", [(1, "dw", 3, 57, 8), (2, "dw", 2, 61, 8), (3, "ou", 2, 64, 4), (6, "dw", 3, 131, 8), (6, "dw", 1, 33, 16),
+                                           (4, "dw", 2, 61, 8), (5, "ou", 2, 64, 4), (7, "dw", 2, 57, 8), (8, "ou", 1, 33, 16)])
 def test_fused_girsanov_update_equals_two_kernel_update(amd, rng, d, kind, B, T, R0):
     """
     update_girsanov_sites inside the backward sweep (mfgm_packed_selinv_girsanov) against the refresh + moment-array update
