@@ -1,7 +1,8 @@
 """
-CPU tests of HarmonicOscillator, Constant and Product (vidp_amd.kernels) and of Sums holding them: constructor checks, the torch
-closed forms against the NumPy restatement tests/np_kernels_ext.py, A against the matrix exponential of the Kronecker-sum generator,
-the exact-zero Q of the noise-free kernels, and the f-covariance of the state-space prior against the dense covariance function.
+CPU tests of HarmonicOscillator, Constant and Product (vidp_amd.kernels), of Sums holding them and of Matern-only trees: constructor
+checks, the torch closed forms against the NumPy restatement tests/np_kernels_ext.py, A against the matrix exponential of the
+Kronecker-sum generator, the exact-zero Q of the noise-free kernels, and the f-covariance of the state-space prior against the dense
+covariance function.
 """
 import numpy as np
 import pytest
@@ -34,12 +35,21 @@ def kernels_pair(name):
             "m32m52": lambda: P([m.Matern32(0.9, 1.2), m.Matern52(1.4, 0.7)]),
             "m32cho": lambda: P([m.Matern32(0.9, 1.2), C(2.0), HO(0.8, 1.3)]),
             "ou_c_ho": lambda: S([m.OrnsteinUhlenbeck(1.3, 0.6), C(0.5), HO(1.0, 4.0)]),
+            # Matern-only trees: the same closed forms, device-built by k_stationary_ssm up to d = 8
+            "m12": lambda: m.Matern12(0.8, 2.0),
+            "m32": lambda: m.Matern32(0.7, 1.3),
+            "m52": lambda: m.Matern52(1.4, 0.7),
+            "m12_m32_m52": lambda: S([m.Matern12(0.8, 2.0), m.Matern32(0.7, 1.3), m.Matern52(1.4, 0.7)]),
+            # (variances that sum to 9: each of the 39 transitions of the f-covariance test adds up to 3 jitters to var f, 1.2e-4 in all,
+            #  and that test allows 1e-5 (max |k| + |k|) = 1.8e-4 on the diagonal)
+            "m52x3": lambda: S([m.Matern52(1.4, 2.0), m.Matern52(0.3, 4.0), m.Matern52(2.5, 3.0)]),
         }[name]()
     return mk(K, K), mk(np_kernels, E)
 
 
 DIMS = {"c": 1, "ho": 2, "m52c": 3, "m32ho": 4, "m52_m12ho": 5, "m52ho": 6, "m32ho_m52": 7, "hom32ho": 8, "m52ho_m52": 9,
-        "m52ho_m32ho": 10, "d11": 11, "d12": 12, "sum_x_ho": 6, "m32m52": 6, "m32cho": 4, "ou_c_ho": 4}
+        "m52ho_m32ho": 10, "d11": 11, "d12": 12, "sum_x_ho": 6, "m32m52": 6, "m32cho": 4, "ou_c_ho": 4,
+        "m12": 1, "m32": 2, "m52": 3, "m12_m32_m52": 6, "m52x3": 9}
 
 
 def test_constructor_checks_match_the_reference():
@@ -121,10 +131,11 @@ def test_quasi_periodic_q_is_the_matern_q_times_the_oscillator_variance():
     assert bool((Q[:, 0:3:2, 1:4:2] == 0).all())   # the oscillator's off-diagonal stays exactly zero
 
 
-F_COV_CASES = ([(n, 0.0) for n in ["c", "ho", "m32ho", "m52_m12ho", "m52ho", "hom32ho", "d12", "sum_x_ho", "m32m52", "m32cho", "ou_c_ho"]]
+F_COV_CASES = ([(n, 0.0) for n in ["c", "ho", "m32ho", "m52_m12ho", "m52ho", "hom32ho", "d12", "sum_x_ho", "m32m52", "m32cho", "ou_c_ho",
+                                          "m12_m32_m52", "m52x3"]]
                # with a jitter only trees whose every term has a Matern factor: a noise-free term integrates the jitter as a random walk
                # (checked on its own below)
-               + [(n, 1e-6) for n in ["m32ho", "m52_m12ho", "m52ho", "d12", "sum_x_ho", "m32m52", "m32cho"]])
+               + [(n, 1e-6) for n in ["m32ho", "m52_m12ho", "m52ho", "d12", "sum_x_ho", "m32m52", "m32cho", "m12_m32_m52", "m52x3"]])
 
 
 @pytest.mark.parametrize("name,jitter", F_COV_CASES)

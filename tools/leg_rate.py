@@ -2,7 +2,7 @@
 yardsticks on the same grid:
 
     leg         the new launch: one matrix exponential, Q, chol Q and offset per transition, outputs preallocated
-    torch       the same kernel object through the steps of StationaryKernel._state_space_model_wide on _generic_local:
+    torch       the same kernel object through StationaryKernel._state_space_model_wide's steps on the torch transition statistics:
                 torch.linalg.matrix_exp on [B (T-1), d, d], batched products and Cholesky -- what a user gets without the kernels
     floor       mfgm_packed_kernel_ssm on a Matern tree of the same d: the same stores with closed-form transitions
 
@@ -83,10 +83,8 @@ def interleaved(cands, reps):
 def case(d, B, T, grid, reps, torch_reps):
     import vidp_amd
     from vidp_amd import kernels as K
-    from vidp_amd import linalg
     from vidp_amd._lib import FULL, TRI, VEC
     from vidp_amd.packed import Plan, _ptr, _stream
-    from vidp_amd.state_space_model import StateSpaceModel
     lib = vidp_amd._lib.load()
     check = vidp_amd._lib.check
     rng = np.random.default_rng(d * 1000 + B)
@@ -110,19 +108,14 @@ def case(d, B, T, grid, reps, torch_reps):
     def floor():
         check(lib.mfgm_packed_kernel_ssm(plan.h, ctypes.byref(kt), _ptr(dts), *(_ptr(o) for o in out), _ptr(plan.info), _stream()), "floor")
 
-    eye = torch.eye(d, dtype=torch.float64, device="cuda")
     mean = gk.state_mean.cuda()
-    chol0 = linalg.cholesky(gk.initial_covariance_matrix().cuda()).expand(B, d, d).contiguous()
+    P0 = gk.initial_covariance_matrix().cuda()
 
     def torch_route():
-        # the steps of StationaryKernel._state_space_model_wide on _generic_local, i.e. on _parts' torch.linalg.matrix_exp
-        # (_state_space_model_wide itself would call transition_statistics_local, which is the HIP k_leg_transitions here)
-        A, Q = gk._generic_local(dts)
-        zero = (Q == 0).all(dim=-1).all(dim=-1)
-        chol = linalg.cholesky(torch.where(zero[..., None, None], eye, Q))
-        chol = torch.where(zero[..., None, None], torch.zeros_like(chol), chol)
-        off = mean - torch.einsum("...ij,j->...i", A, mean)
-        return StateSpaceModel(mean.expand(B, d).contiguous(), chol0, A, off, chol, plan=plan)
+        # StationaryKernel._state_space_model_wide on the base class's transition statistics, i.e. on _parts' torch.linalg.matrix_exp
+        # (_state_space_model_wide itself would call gk.transition_statistics_local, which is the HIP k_leg_transitions here)
+        A, Q = K.StationaryKernel.transition_statistics_local(gk, dts)
+        return K._model_from_torch(A, Q, mean, mean, P0, plan, (B,))
 
     times = interleaved({"leg": (leg, reps), "torch": (torch_route, torch_reps), "floor": (floor, reps)}, reps)
     plan.check_info()

@@ -1,15 +1,17 @@
 """
-Host-side mirror of the stationary SDE kernels on the path (markovflow/kernels/matern.py: `Matern12`,
-`OrnsteinUhlenbeck`, `Matern32`, `Matern52`; markovflow/kernels/sde_kernel.py: `StationaryKernel`, `Sum`).
-`state_space_model(time_points)` evaluates the closed-form matrix exponentials, the process covariances and their
-Cholesky factors in one HIP kernel (k_stationary_ssm) directly in the packed layout.
+Host-side mirror of the SDE kernels on the path (markovflow/kernels/matern.py: `Matern12`, `OrnsteinUhlenbeck`, `Matern32`,
+`Matern52`; kernels/periodic.py `HarmonicOscillator`; kernels/constant.py `Constant`; kernels/sde_kernel.py: `StationaryKernel`,
+`Sum`, `Product`; kernels/latent_exp_generated.py `LatentExponentiallyGenerated`; kernels/piecewise_stationary.py).
 
-Seasonal priors (markovflow/kernels/periodic.py `HarmonicOscillator`, kernels/constant.py `Constant`, kernels/sde_kernel.py
-`Product`) and any Sum / Product tree holding them go through the generic term kernel k_kernel_ssm (mfgm_packed_kernel_ssm) for
-state_dim <= 8 and through the torch closed forms otherwise.
+One closed-form route: a kernel class states its dynamics once, in `_parts` (A, Pinf and Q without jitter under the exact-Q rule of
+DESIGN.md section 12, in torch, differentiable through the hyper-parameter leaves), `_emission_row`, `_terms` and `feedback_matrix`;
+`StationaryKernel` derives the steady-state covariance, `transition_statistics_local`, `differentiable_ssm`, the emission model and
+the torch construction beyond state_dim 8 from them.
 
-Learnable dynamics (markovflow/kernels/latent_exp_generated.py `LatentExponentiallyGenerated`) have no closed-form transition: the
-matrix exponentials of every transition are evaluated by k_leg_ssm (mfgm_packed_leg_ssm).
+`state_space_model(time_points)` for state_dim <= 8 is one HIP launch that evaluates the transitions, the process covariances and
+their Cholesky factors directly in the packed layout: k_stationary_ssm for Matern / OU trees, the term kernel k_kernel_ssm
+(mfgm_packed_kernel_ssm) for any other Sum / Product tree `_terms()` expresses, k_leg_ssm (mfgm_packed_leg_ssm)
+for the learnable dynamics, which have no closed-form transition, and k_piecewise_ssm for change-point priors.
 """
 import ctypes
 import math
@@ -24,10 +26,63 @@ from .state_space_model import StateSpaceModel, _flat
 from .variational_cvi_sde import _ssm_from_packed
 
 
+_FACTOR_DIM = {_lib.FACTOR_MATERN12: 1, _lib.FACTOR_MATERN32: 2, _lib.FACTOR_MATERN52: 3, _lib.FACTOR_CONSTANT: 1,
+               _lib.FACTOR_HARMONIC: 2}
+_NOT_PD = ("the process covariance Q of the kernel's state-space model is neither positive definite nor exactly zero "
+           "(e.g. a Sum of a Matern and a HarmonicOscillator): set a jitter on the kernel")
+
+
+# -- the tails every kernel class shares: transition statistics -> model ---------------------------------------------------------------
+def _model_from_packed(plan, packed, batch_shape, not_pd=True):
+    """StateSpaceModel of the packed (A, off, chol) one of the plan's SSM launches returned.  not_pd: a Q that is neither positive
+    definite nor exactly zero raises the "set a jitter" ArithmeticError instead of the plan's own."""
+    try:
+        plan.check_info()
+    except ArithmeticError as e:
+        if not not_pd:
+            raise
+        raise ArithmeticError(_NOT_PD) from e
+    ssm = _ssm_from_packed(plan, *packed)
+    ssm.batch_shape = batch_shape
+    return ssm
+
+
+def _model_from_torch(A, Q, m, mu0, P0, plan, batch_shape):
+    """StateSpaceModel of (A, Q) [B, T - 1, d, d] held in torch: cholesky_or_zero of Q and b = (I - A) m, with m [d] or [B, T - 1, d]
+    the state means at the transitions' left ends; the first state is N(mu0 [d], P0 [d, d] or [B, d, d])."""
+    B, d = A.shape[0], A.shape[-1]
+    zero = (Q == 0).all(dim=-1).all(dim=-1)[..., None, None]
+    chol = linalg.cholesky(torch.where(zero, torch.eye(d, dtype=Q.dtype, device=Q.device), Q))
+    chol = torch.where(zero, torch.zeros_like(chol), chol)
+    off = m - (A @ m[..., None])[..., 0]
+    ssm = StateSpaceModel(mu0.expand(B, d).contiguous(), linalg.cholesky(P0).expand(B, d, d).contiguous(), A, off, chol, plan=plan)
+    ssm.batch_shape = batch_shape
+    return ssm
+
+
+def _tape_model(A, Qterm, exact, Pinf0, m, mu0, jitter, plan):
+    """tape.TapeSSM of one chain from differentiable A, Qterm = Pinf - A Pinf A^T [T - 1, d, d] (exactly zero when `exact`) and
+    Pinf0 [d, d] of the first state: Q = Qterm + jitter, zero where that is exact, b = (I - A) m with m as in _model_from_torch."""
+    from . import tape
+    jit = jitter * torch.eye(A.shape[-1], dtype=torch.float64, device=A.device)
+    Q = Qterm + jit
+    b = m - (A @ m[..., None])[..., 0]
+    cq = torch.zeros_like(Q) if (exact and jitter == 0.0) else tape.cholesky(0.5 * (Q + Q.transpose(-1, -2)))
+    return tape.TapeSSM(mu0[None], tape.cholesky(Pinf0 + jit)[None], A[None], b[None], cq[None], plan=plan)
+
+
+def _emission_model(H, time_points):
+    """EmissionModel of the time-invariant H [output_dim, state_dim], tiled over the time points."""
+    H = H.to(time_points.device)
+    return EmissionModel(H.expand(tuple(time_points.shape) + tuple(H.shape)).contiguous(), constant_matrix=H)
+
+
 class StationaryKernel:
-    """kernels/sde_kernel.py:367-475."""
+    """kernels/sde_kernel.py:367-475.  A kernel class states its dynamics in _parts, _emission_row, _terms and feedback_matrix; every
+    other member is derived from them here."""
 
     state_dim = None
+    _matern_tree = True      # only Matern / OU leaves and Sums of them: what selects k_stationary_ssm in state_space_model
 
     def __init__(self, output_dim=1, jitter=0.0, state_mean=None):
         if output_dim != 1:
@@ -35,10 +90,6 @@ class StationaryKernel:
         self.output_dim = output_dim
         self.jitter = float(jitter)
         self._state_mean = state_mean
-
-    # components: list of (order, lam, var) -------------------------------------------------------------
-    def _components(self):
-        raise NotImplementedError
 
     @property
     def state_mean(self):
@@ -49,214 +100,25 @@ class StationaryKernel:
     def set_state_mean(self, state_mean, trainable=False):
         self._state_mean = state_mean
 
-    def _spec(self):
-        comps = self._components()
-        if len(comps) > 8 or self.state_dim > 8:
-            raise ValueError("the HIP path supports up to 8 components and state_dim <= 8")
-        spec = _lib.KernelSpec()
-        spec.ncomp = len(comps)
-        off = 0
-        for i, (order, lam, var) in enumerate(comps):
-            spec.order[i], spec.offset[i], spec.lam[i], spec.var[i] = order, off, lam, var
-            off += order
-        m = self.state_mean
-        for i in range(self.state_dim):
-            spec.mean[i] = float(m[i])
-        spec.jitter = self.jitter
-        return spec
-
-    def _block_diag(self, blocks):
-        return torch.block_diag(*blocks)
-
-    @property
-    def steady_state_covariance(self):
-        blocks = []
-        for order, lam, var in self._components():
-            if order == 1:
-                blocks.append(torch.tensor([[var]], dtype=torch.float64))
-            elif order == 2:
-                blocks.append(var * torch.tensor([[1.0, 0.0], [0.0, lam ** 2]], dtype=torch.float64))
-            else:
-                l23 = lam ** 2 / 3.0
-                blocks.append(var * torch.tensor([[1.0, 0.0, -l23], [0.0, l23, 0.0], [-l23, 0.0, lam ** 4]], dtype=torch.float64))
-        return self._block_diag(blocks)
-
-    @property
-    def feedback_matrix(self):
-        blocks = []
-        for order, lam, var in self._components():
-            if order == 1:
-                blocks.append(torch.tensor([[-lam]], dtype=torch.float64))
-            elif order == 2:
-                blocks.append(torch.tensor([[0.0, 1.0], [-lam ** 2, -2.0 * lam]], dtype=torch.float64))
-            else:
-                blocks.append(torch.tensor([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [-lam ** 3, -3.0 * lam ** 2, -3.0 * lam]],
-                                           dtype=torch.float64))
-        return self._block_diag(blocks)
-
-    def state_space_model(self, time_points, plan=None):
-        """SDEKernel.state_space_model (sde_kernel.py:153-171): prior SSM at the given (sorted) time points [..., T]."""
-        t, bs = _flat(time_points, 1)
-        B, T = t.shape
-        if plan is None:
-            plan = Plan(B, T, self.state_dim, device=t.device)
-        dts = (t[:, 1:] - t[:, :-1]).contiguous()
-        if self.state_dim > 8:
-            return self._state_space_model_wide(dts, bs, plan)
-        A, off, chol = plan.stationary_ssm(self._spec(), dts)
-        plan.check_info()
-        ssm = _ssm_from_packed(plan, A, off, chol)
-        ssm.batch_shape = bs
-        return ssm
-
-    def _state_space_model_wide(self, dts, bs, plan):
-        """
-        state_dim > 8 (e.g. the reference's Sum of ten Matern-5/2, d = 30): the fused k_stationary_ssm kernel is
-        specialised for d <= 8, so this one-off model construction uses the per-element closed forms in torch
-        (block-diagonal A, Q = Pinf - A Pinf A^T + jitter, cholesky_or_zero, b = (I - A) m); the sweeps that follow
-        run in the wide HIP kernels.
-        """
-        dev = dts.device
-        d = self.state_dim
-        A, Q = self.transition_statistics_local(dts)
-        zero = (Q == 0).all(dim=-1).all(dim=-1)
-        eye = torch.eye(d, dtype=Q.dtype, device=dev)
-        chol = linalg.cholesky(torch.where(zero[..., None, None], eye, Q))
-        chol = torch.where(zero[..., None, None], torch.zeros_like(chol), chol)
-        m = self.state_mean.to(dev)
-        off = m - torch.einsum("...ij,j->...i", A, m)
-        B = dts.shape[0]
-        P0 = self.initial_covariance_matrix().to(dev)
-        ssm = StateSpaceModel(m.expand(B, d).contiguous(), linalg.cholesky(P0).expand(B, d, d).contiguous(), A, off, chol,
-                              plan=plan)
-        ssm.batch_shape = bs
-        return ssm
-
-    def transition_statistics(self, transition_times, time_deltas):
-        """(A_k, Q_k) (sde_kernel.py:421-446), natural tensors."""
-        td, bs = _flat(time_deltas, 1)
-        B, N = td.shape
-        t = torch.cat([torch.zeros((B, 1), dtype=td.dtype, device=td.device), torch.cumsum(td, dim=1)], dim=1)
-        ssm = self.state_space_model(t)
-        A = ssm.state_transitions
-        c = ssm.cholesky_process_covariances
-        return A.reshape(bs + tuple(A.shape[1:])), (c @ c.transpose(-1, -2)).reshape(bs + tuple(c.shape[1:]))
-
-    def state_transitions(self, transition_times, time_deltas):
-        return self.transition_statistics(transition_times, time_deltas)[0]
-
-    def transition_statistics_local(self, time_deltas):
-        """
-        (A, Q) for arbitrary, unordered time gaps (any shape [...]) as per-element closed forms in torch: used by the
-        conditionals (prediction between conditioning points, conditionals.py:207-256), which are embarrassingly parallel
-        over query points.  Same formulas as k_stationary_ssm.
-        """
-        dt = time_deltas[..., None, None]
-        blocks = []
-        for order, lam, var in self._components():
-            ex = torch.exp(-lam * dt)
-            if order == 1:
-                blocks.append(ex * torch.ones((1, 1), dtype=dt.dtype, device=dt.device))
-            elif order == 2:
-                N = torch.tensor([[lam, 1.0], [-lam ** 2, -lam]], dtype=dt.dtype, device=dt.device)
-                blocks.append(ex * (torch.eye(2, dtype=dt.dtype, device=dt.device) + N * dt))
-            else:
-                N = torch.tensor([[lam, 1.0, 0.0], [0.0, lam, 1.0], [-lam ** 3, -3.0 * lam ** 2, -2.0 * lam]], dtype=dt.dtype,
-                                 device=dt.device)
-                blocks.append(ex * (torch.eye(3, dtype=dt.dtype, device=dt.device) + N * dt + (N @ N) * (0.5 * dt * dt)))
-        d = self.state_dim
-        A = torch.zeros(tuple(time_deltas.shape) + (d, d), dtype=dt.dtype, device=dt.device)
-        o = 0
-        for blk in blocks:
-            k = blk.shape[-1]
-            A[..., o:o + k, o:o + k] = blk
-            o += k
-        Pinf = self.steady_state_covariance.to(dt.device)
-        Q = Pinf - A @ Pinf @ A.transpose(-1, -2) + self.jitter * torch.eye(d, dtype=dt.dtype, device=dt.device)
-        return A, Q
-
-    # -- hyper-parameters as leaves of a torch graph (the reference differentiates classic_elbo through the kernel's tf.Variables with a
-    #    GradientTape, tests/integration/models/test_variational_cvi.py:93-110) ------------------------------------------------------------
-    def hyperparameter_leaves(self, device="cpu"):
-        """{name: 0-dim tensor with requires_grad} of this kernel's trainable hyper-parameters (a list of such dicts for a Sum)."""
+    # -- the primitives: the Matern / OU leaf, whose subclasses give (order, lam, var) ---------------------------------------------------
+    def _components(self):
+        """[(order, lam, var)] of the Matern / OU blocks of this kernel, in state order."""
         raise NotImplementedError
 
     def _components_t(self, leaves):
         """[(order, lam, var)] with lam / var torch expressions of the leaves (the differentiable twin of _components)."""
         raise NotImplementedError
 
-    def differentiable_ssm(self, time_points, leaves=None, plan=None):
-        """(tape.TapeSSM, leaves): the prior state-space model at the sorted time points [T] (one chain) as a differentiable function of
-        the hyper-parameter leaves -- the closed forms of k_stationary_ssm (A = e^{-lam dt}(I + N dt + N^2 dt^2 / 2), Q = Pinf - A Pinf A^T
-        + jitter) in torch, d <= 8; everything sequential in time downstream (marginals, log-determinants) goes through vidp_amd.tape,
-        i.e. the HIP sweeps with exact backward passes."""
-        from . import tape
-        t = time_points.reshape(-1)
-        dev = t.device
-        if leaves is None:
-            leaves = self.hyperparameter_leaves(dev)
-        dt = (t[1:] - t[:-1])[:, None, None]
-        d = self.state_dim
-        A = torch.zeros((t.numel() - 1, d, d), dtype=torch.float64, device=dev)
-        Pinf = torch.zeros((d, d), dtype=torch.float64, device=dev)
-        o = 0
-        for order, lam, var in self._components_t(leaves):
-            ex = torch.exp(-lam * dt)
-            eye = torch.eye(order, dtype=torch.float64, device=dev)
-            one, zero = torch.ones_like(lam), torch.zeros_like(lam)
-            if order == 1:
-                blk, pinf = ex * eye, var.reshape(1, 1)
-            elif order == 2:
-                N = torch.stack([torch.stack([lam, one]), torch.stack([-lam ** 2, -lam])])
-                blk = ex * (eye + N * dt)
-                pinf = var * torch.stack([torch.stack([one, zero]), torch.stack([zero, lam ** 2])])
-            else:
-                N = torch.stack([torch.stack([lam, one, zero]), torch.stack([zero, lam, one]),
-                                 torch.stack([-lam ** 3, -3.0 * lam ** 2, -2.0 * lam])])
-                blk = ex * (eye + N * dt + (N @ N) * (0.5 * dt * dt))
-                l23 = lam ** 2 / 3.0
-                pinf = var * torch.stack([torch.stack([one, zero, -l23]), torch.stack([zero, l23, zero]), torch.stack([-l23, zero, lam ** 4])])
-            A = A + torch.nn.functional.pad(blk, (o, d - o - order, o, d - o - order))
-            Pinf = Pinf + torch.nn.functional.pad(pinf, (o, d - o - order, o, d - o - order))
-            o += order
-        jit = self.jitter * torch.eye(d, dtype=torch.float64, device=dev)
-        Q = Pinf - A @ Pinf @ A.transpose(-1, -2) + jit
-        m = self.state_mean.to(dev)
-        b = m - (A @ m[:, None])[..., 0]
-        ssm = tape.TapeSSM(m[None], tape.cholesky(Pinf + jit)[None], A[None], b[None], tape.cholesky(0.5 * (Q + Q.transpose(-1, -2)))[None], plan=plan)
-        return ssm, leaves
-
-    def initial_mean(self, batch_shape=()):
-        return self.state_mean.expand(tuple(batch_shape) + (self.state_dim,))
-
-    def initial_covariance_matrix(self):
-        """Pinf + jitter (sde_kernel.py:402-419)."""
-        return self.steady_state_covariance + self.jitter * torch.eye(self.state_dim, dtype=torch.float64)
-
-    # -- the time-aware forms the models call (SDEKernel.initial_covariance / transition_statistics take the time of the state or of the
-    #    transition's left end, sde_kernel.py:113-151): a stationary kernel ignores the times --------------------------------------------
-    def initial_covariance(self, initial_time_point=None):
-        return self.initial_covariance_matrix()
-
-    def transition_statistics_at(self, transition_times, time_deltas):
-        """(A, Q) of the transitions that start at transition_times and last time_deltas (any shape, unordered)."""
-        return self.transition_statistics_local(time_deltas)
-
-    def generate_emission_model(self, time_points):
-        """H = [1, 0, ...] per component, tiled over the time points (sde_kernel.py:173-211, 670-687)."""
-        h = torch.zeros((1, self.state_dim), dtype=torch.float64, device=time_points.device)
-        off = 0
-        for order, _, _ in self._components():
-            h[0, off] = 1.0
-            off += order
-        return EmissionModel(h.expand(tuple(time_points.shape) + (1, self.state_dim)).contiguous(), constant_matrix=h)
-
-    # -- the generic (term-tree) route: every kernel, primitive or combined, as parts of the exact-Q rule ------------------------------
-    _matern_tree = True      # only Matern / OU leaves and Sums of them: the k_stationary_ssm route above
+    def hyperparameter_leaves(self, device="cpu"):
+        """{name: 0-dim tensor with requires_grad} of this kernel's trainable hyper-parameters (a list of such dicts for a Sum): the
+        leaves of a torch graph (the reference differentiates classic_elbo through the kernel's tf.Variables with a GradientTape,
+        tests/integration/models/test_variational_cvi.py:93-110)."""
+        raise NotImplementedError
 
     def _parts(self, dt, leaves=None):
         """(A [..., d, d], Pinf [d, d], Qterm [..., d, d], exact) at the time gaps dt [...]: Qterm = Pinf - A Pinf A^T without jitter
-        (exactly zero when `exact`).  leaves: hyperparameter_leaves() to differentiate through, or None for the current values."""
+        (exactly zero when `exact`).  leaves: hyperparameter_leaves() to differentiate through, or None for the current values.
+        Here the formulas of k_stationary_ssm: A = e^{-lam dt} (I + N dt + N^2 dt^2 / 2)."""
         comps = self._components() if leaves is None else self._components_t(leaves)
         (order, lam, var), = comps
         lam = torch.as_tensor(lam, dtype=torch.float64, device=dt.device)
@@ -290,26 +152,31 @@ class StationaryKernel:
         (order, lam, var), = self._components()
         return [[(order, float(lam), float(var))]]
 
-    def _generic_ssm(self, time_points, plan=None):
-        t, bs = _flat(time_points, 1)
-        B, T = t.shape
-        if plan is None:
-            plan = Plan(B, T, self.state_dim, device=t.device)
-        dts = (t[:, 1:] - t[:, :-1]).contiguous()
-        terms = self._terms() if self.state_dim <= 8 else None
-        if terms is None or len(terms) > 8:
-            try:
-                return self._state_space_model_wide(dts, bs, plan)
-            except ArithmeticError as e:
-                raise ArithmeticError(_NOT_PD) from e
-        A, off_, chol = plan.kernel_ssm(self._terms_struct(terms), dts)
-        try:
-            plan.check_info()
-        except ArithmeticError as e:
-            raise ArithmeticError(_NOT_PD) from e
-        ssm = _ssm_from_packed(plan, A, off_, chol)
-        ssm.batch_shape = bs
-        return ssm
+    @property
+    def feedback_matrix(self):
+        (order, lam, _), = self._components()
+        if order == 1:
+            return torch.tensor([[-lam]], dtype=torch.float64)
+        if order == 2:
+            return torch.tensor([[0.0, 1.0], [-lam ** 2, -2.0 * lam]], dtype=torch.float64)
+        return torch.tensor([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [-lam ** 3, -3.0 * lam ** 2, -3.0 * lam]], dtype=torch.float64)
+
+    # -- the device structs ---------------------------------------------------------------------------------------------------------------
+    def _spec(self):
+        comps = self._components()
+        if len(comps) > 8 or self.state_dim > 8:
+            raise ValueError("the HIP path supports up to 8 components and state_dim <= 8")
+        spec = _lib.KernelSpec()
+        spec.ncomp = len(comps)
+        off = 0
+        for i, (order, lam, var) in enumerate(comps):
+            spec.order[i], spec.offset[i], spec.lam[i], spec.var[i] = order, off, lam, var
+            off += order
+        m = self.state_mean
+        for i in range(self.state_dim):
+            spec.mean[i] = float(m[i])
+        spec.jitter = self.jitter
+        return spec
 
     def _terms_struct(self, terms=None):
         """mfgm_kernel_terms of this kernel (any tree _terms() expresses, Matern-only ones included)."""
@@ -332,26 +199,94 @@ class StationaryKernel:
         kt.jitter = self.jitter
         return kt
 
-    def _generic_local(self, time_deltas):
-        A, _, Qt, _ = self._parts(time_deltas)
-        d = self.state_dim
-        return A, Qt + self.jitter * torch.eye(d, dtype=A.dtype, device=A.device)
+    # -- derived from the primitives ------------------------------------------------------------------------------------------------------
+    @property
+    def steady_state_covariance(self):
+        return self._parts(torch.zeros(1, dtype=torch.float64))[1].detach()
 
-    def _generic_differentiable_ssm(self, time_points, leaves=None, plan=None):
-        from . import tape
+    def state_space_model(self, time_points, plan=None):
+        """SDEKernel.state_space_model (sde_kernel.py:153-171): prior SSM at the given (sorted) time points [..., T].  state_dim <= 8:
+        one launch, k_stationary_ssm for a Matern tree and k_kernel_ssm for any other tree _terms() expresses; otherwise the torch
+        closed forms (_state_space_model_wide)."""
+        t, bs = _flat(time_points, 1)
+        B, T = t.shape
+        if plan is None:
+            plan = Plan(B, T, self.state_dim, device=t.device)
+        dts = (t[:, 1:] - t[:, :-1]).contiguous()
+        if self._matern_tree:
+            if self.state_dim > 8:
+                return self._state_space_model_wide(dts, bs, plan)
+            return _model_from_packed(plan, plan.stationary_ssm(self._spec(), dts), bs, not_pd=False)
+        terms = self._terms() if self.state_dim <= 8 else None
+        if terms is None or len(terms) > 8:
+            try:
+                return self._state_space_model_wide(dts, bs, plan)
+            except ArithmeticError as e:
+                raise ArithmeticError(_NOT_PD) from e
+        return _model_from_packed(plan, plan.kernel_ssm(self._terms_struct(terms), dts), bs)
+
+    def _state_space_model_wide(self, dts, bs, plan):
+        """
+        state_dim > 8 (e.g. the reference's Sum of ten Matern-5/2, d = 30) or a tree the term struct cannot express: the fused kernels
+        are specialised for d <= 8, so this one-off model construction uses the per-element closed forms in torch (Q under the exact-Q
+        rule + jitter, cholesky_or_zero, b = (I - A) m); the sweeps that follow run in the wide HIP kernels.
+        """
+        A, Q = self.transition_statistics_local(dts)
+        m = self.state_mean.to(dts.device)
+        return _model_from_torch(A, Q, m, m, self.initial_covariance_matrix().to(dts.device), plan, bs)
+
+    def transition_statistics(self, transition_times, time_deltas):
+        """(A_k, Q_k) (sde_kernel.py:421-446), natural tensors."""
+        td, bs = _flat(time_deltas, 1)
+        B, N = td.shape
+        t = torch.cat([torch.zeros((B, 1), dtype=td.dtype, device=td.device), torch.cumsum(td, dim=1)], dim=1)
+        ssm = self.state_space_model(t)
+        A = ssm.state_transitions
+        c = ssm.cholesky_process_covariances
+        return A.reshape(bs + tuple(A.shape[1:])), (c @ c.transpose(-1, -2)).reshape(bs + tuple(c.shape[1:]))
+
+    def state_transitions(self, transition_times, time_deltas):
+        return self.transition_statistics(transition_times, time_deltas)[0]
+
+    def transition_statistics_local(self, time_deltas):
+        """
+        (A, Q) for arbitrary, unordered time gaps (any shape [...]) as per-element closed forms in torch under the exact-Q rule
+        (DESIGN.md section 12): used by the conditionals (prediction between conditioning points, conditionals.py:207-256), which are
+        embarrassingly parallel over query points.  Same formulas as k_stationary_ssm and k_kernel_ssm.
+        """
+        A, _, Qterm, _ = self._parts(time_deltas)
+        return A, Qterm + self.jitter * torch.eye(self.state_dim, dtype=A.dtype, device=A.device)
+
+    def differentiable_ssm(self, time_points, leaves=None, plan=None):
+        """(tape.TapeSSM, leaves): the prior state-space model at the sorted time points [T] (one chain) as a differentiable function of
+        the hyper-parameter leaves -- _parts in torch, d <= 8; everything sequential in time downstream (marginals, log-determinants)
+        goes through vidp_amd.tape, i.e. the HIP sweeps with exact backward passes."""
         t = time_points.reshape(-1)
-        dev = t.device
         if leaves is None:
-            leaves = self.hyperparameter_leaves(dev)
-        A, Pinf, Qt, exact = self._parts(t[1:] - t[:-1], leaves)
-        d = self.state_dim
-        jit = self.jitter * torch.eye(d, dtype=torch.float64, device=dev)
-        Q = Qt + jit
-        m = self.state_mean.to(dev)
-        b = m - (A @ m[:, None])[..., 0]
-        cq = torch.zeros_like(Q) if (exact and self.jitter == 0.0) else tape.cholesky(0.5 * (Q + Q.transpose(-1, -2)))
-        ssm = tape.TapeSSM(m[None], tape.cholesky(Pinf + jit)[None], A[None], b[None], cq[None], plan=plan)
-        return ssm, leaves
+            leaves = self.hyperparameter_leaves(t.device)
+        A, Pinf, Qterm, exact = self._parts(t[1:] - t[:-1], leaves)
+        m = self.state_mean.to(t.device)
+        return _tape_model(A, Qterm, exact, Pinf, m, m, self.jitter, plan), leaves
+
+    def initial_mean(self, batch_shape=()):
+        return self.state_mean.expand(tuple(batch_shape) + (self.state_dim,))
+
+    def initial_covariance_matrix(self):
+        """Pinf + jitter (sde_kernel.py:402-419)."""
+        return self.steady_state_covariance + self.jitter * torch.eye(self.state_dim, dtype=torch.float64)
+
+    # -- the time-aware forms the models call (SDEKernel.initial_covariance / transition_statistics take the time of the state or of the
+    #    transition's left end, sde_kernel.py:113-151): a stationary kernel ignores the times --------------------------------------------
+    def initial_covariance(self, initial_time_point=None):
+        return self.initial_covariance_matrix()
+
+    def transition_statistics_at(self, transition_times, time_deltas):
+        """(A, Q) of the transitions that start at transition_times and last time_deltas (any shape, unordered)."""
+        return self.transition_statistics_local(time_deltas)
+
+    def generate_emission_model(self, time_points):
+        """H = _emission_row(), tiled over the time points (sde_kernel.py:173-211, 670-687)."""
+        return _emission_model(self._emission_row()[None], time_points)
 
 
 def _check(lengthscale, variance):
@@ -460,20 +395,6 @@ class Sum(StationaryKernel):
     def hyperparameter_leaves(self, device="cpu"):
         return [k.hyperparameter_leaves(device) for k in self.kernels]
 
-    def _components_t(self, leaves):
-        out = []
-        for k, lv in zip(self.kernels, leaves):
-            out.extend(k._components_t(lv))
-        return out
-
-    def _spec(self):
-        spec = super()._spec()
-        # each component kernel adds its own jitter to its Q block; Sum adds its own on top (sde_kernel.py:640-656)
-        if any(k.jitter != 0.0 for k in self.kernels):
-            raise ValueError("per-component jitter inside Sum is not supported on the HIP path; set it on the Sum")
-        return spec
-
-    # -- children beyond Matern / OU (HarmonicOscillator, Constant, Product): the term-tree route -------------------------------------
     @property
     def _matern_tree(self):
         return all(k._matern_tree for k in self.kernels)
@@ -497,44 +418,15 @@ class Sum(StationaryKernel):
         return out
 
     @property
-    def steady_state_covariance(self):
-        if self._matern_tree:
-            return super().steady_state_covariance
-        return self._parts(torch.zeros(1, dtype=torch.float64))[1].detach()
-
-    @property
     def feedback_matrix(self):
-        if self._matern_tree:
-            return super().feedback_matrix
         return torch.block_diag(*[k.feedback_matrix for k in self.kernels])
 
     def state_space_model(self, time_points, plan=None):
-        if self._matern_tree:
-            return super().state_space_model(time_points, plan)
-        if any(k.jitter != 0.0 for k in self.kernels):
+        # each component kernel adds its own jitter to its Q block; Sum adds its own on top (sde_kernel.py:640-656).  (The torch build
+        # of a Matern tree beyond state_dim 8 has always used the Sum's jitter alone.)
+        if any(k.jitter != 0.0 for k in self.kernels) and not (self._matern_tree and self.state_dim > 8):
             raise ValueError("per-component jitter inside Sum is not supported on the HIP path; set it on the Sum")
-        return self._generic_ssm(time_points, plan)
-
-    def transition_statistics_local(self, time_deltas):
-        if self._matern_tree:
-            return super().transition_statistics_local(time_deltas)
-        return self._generic_local(time_deltas)
-
-    def differentiable_ssm(self, time_points, leaves=None, plan=None):
-        if self._matern_tree:
-            return super().differentiable_ssm(time_points, leaves, plan)
-        return self._generic_differentiable_ssm(time_points, leaves, plan)
-
-    def generate_emission_model(self, time_points):
-        if self._matern_tree:
-            return super().generate_emission_model(time_points)
-        return _GenericKernel.generate_emission_model(self, time_points)
-
-
-_FACTOR_DIM = {_lib.FACTOR_MATERN12: 1, _lib.FACTOR_MATERN32: 2, _lib.FACTOR_MATERN52: 3, _lib.FACTOR_CONSTANT: 1,
-               _lib.FACTOR_HARMONIC: 2}
-_NOT_PD = ("the process covariance Q of the kernel's state-space model is neither positive definite nor exactly zero "
-           "(e.g. a Sum of a Matern and a HarmonicOscillator): set a jitter on the kernel")
+        return super().state_space_model(time_points, plan)
 
 
 def _kron(X, Y):
@@ -557,34 +449,11 @@ def _block_diag_b(mats):
     return out
 
 
-class _GenericKernel(StationaryKernel):
-    """The members the models use, on the term-tree route (HIP k_kernel_ssm for d <= 8, torch closed forms otherwise)."""
-
-    _matern_tree = False
-
-    @property
-    def steady_state_covariance(self):
-        return self._parts(torch.zeros(1, dtype=torch.float64))[1].detach()
-
-    def state_space_model(self, time_points, plan=None):
-        return self._generic_ssm(time_points, plan)
-
-    def transition_statistics_local(self, time_deltas):
-        """(A, Q) for arbitrary, unordered time gaps under the exact-Q rule, the formulas of k_kernel_ssm."""
-        return self._generic_local(time_deltas)
-
-    def differentiable_ssm(self, time_points, leaves=None, plan=None):
-        return self._generic_differentiable_ssm(time_points, leaves, plan)
-
-    def generate_emission_model(self, time_points):
-        h = self._emission_row().to(time_points.device)[None]
-        return EmissionModel(h.expand(tuple(time_points.shape) + (1, self.state_dim)).contiguous(), constant_matrix=h)
-
-
-class HarmonicOscillator(_GenericKernel):
+class HarmonicOscillator(StationaryKernel):
     """periodic.py:27-203: k(tau) = variance cos(2 pi tau / period); lambda = 2 pi / period, A = [[cos, -sin], [sin, cos]](lambda dt),
     Pinf = variance I, H = [1, 0], Q = 0 (+ jitter)."""
     state_dim = 2
+    _matern_tree = False
 
     def __init__(self, variance, period, output_dim=1, jitter=0.0):
         super().__init__(output_dim, jitter)
@@ -616,10 +485,11 @@ class HarmonicOscillator(_GenericKernel):
         return [[(_lib.FACTOR_HARMONIC, 2.0 * math.pi / self.period, self.variance)]]
 
 
-class Constant(_GenericKernel):
+class Constant(StationaryKernel):
     """constant.py:28-153: k(tau) = variance; A = [[1]], Pinf = [[variance]], H = [1], Q = 0 (+ jitter).  feedback_matrix is zero, as in
     the reference code (its docstring says [[1]])."""
     state_dim = 1
+    _matern_tree = False
 
     def __init__(self, variance, output_dim=1, jitter=0.0):
         super().__init__(output_dim, jitter)
@@ -643,7 +513,7 @@ class Constant(_GenericKernel):
         return [[(_lib.FACTOR_CONSTANT, 0.0, self.variance)]]
 
 
-class LatentExponentiallyGenerated(_GenericKernel):
+class LatentExponentiallyGenerated(StationaryKernel):
     """kernels/latent_exp_generated.py:28-142, the LEG-GP kernel of Loper et al. (2020): dx = -1/2 G x dt + N dw with
     G = N N^T + R - R^T for arbitrary N (noise mixing) and R (rotation inducing) [d, d], so feedback_matrix F = -G / 2,
     steady_state_covariance = I, A(dt) = expm(F dt) and Q(dt) = I - A A^T.  The only kernel of the family whose dynamics are free
@@ -656,9 +526,11 @@ class LatentExponentiallyGenerated(_GenericKernel):
     state_dim <= 8 on the device: state_space_model is one launch of mfgm_packed_leg_ssm (scaling-and-squaring Taylor exponential, Q,
     chol Q and the offsets of every transition, DESIGN.md section 17) and transition_statistics_local one of mfgm_leg_transitions;
     for state_dim > 8 or CPU tensors torch.linalg.matrix_exp (and, on the device, the wide sweeps).  _state_space_model_wide calls
-    transition_statistics_local, so on the device with state_dim <= 8 it too takes the HIP transitions; _generic_local is the torch
-    route at any size.  Hyper-parameter gradients go through matrix_exp's backward and the tape.
-    Inside Sum / Product / PiecewiseKernel a LEG child takes the torch routes (_terms() is None)."""
+    transition_statistics_local, so on the device with state_dim <= 8 it too takes the HIP transitions;
+    StationaryKernel.transition_statistics_local is the torch route at any size.  Hyper-parameter gradients go through matrix_exp's
+    backward and the tape.  Inside Sum / Product / PiecewiseKernel a LEG child takes the torch routes (_terms() is None)."""
+
+    _matern_tree = False
 
     def __init__(self, N, R, jitter=0.0, emission=None):
         N = torch.as_tensor(N, dtype=torch.float64).detach().cpu()
@@ -681,10 +553,6 @@ class LatentExponentiallyGenerated(_GenericKernel):
     @property
     def feedback_matrix(self):
         return self._feedback(self.N, self.R)
-
-    @property
-    def steady_state_covariance(self):
-        return torch.eye(self.state_dim, dtype=torch.float64)
 
     def hyperparameter_leaves(self, device="cpu"):
         mk = lambda v: v.clone().to(device).requires_grad_(True)
@@ -722,24 +590,17 @@ class LatentExponentiallyGenerated(_GenericKernel):
     def state_space_model(self, time_points, plan=None):
         t, bs = _flat(time_points, 1)
         if self.state_dim > 8 or not t.is_cuda:
-            return self._generic_ssm(time_points, plan)
+            return super().state_space_model(time_points, plan)
         B, T = t.shape
         if plan is None:
             plan = Plan(B, T, self.state_dim, device=t.device)
-        A, off, chol = plan.leg_ssm(self._spec(), (t[:, 1:] - t[:, :-1]).contiguous())
-        try:
-            plan.check_info()
-        except ArithmeticError as e:
-            raise ArithmeticError(_NOT_PD) from e
-        ssm = _ssm_from_packed(plan, A, off, chol)
-        ssm.batch_shape = bs
-        return ssm
+        return _model_from_packed(plan, plan.leg_ssm(self._spec(), (t[:, 1:] - t[:, :-1]).contiguous()), bs)
 
     def transition_statistics_local(self, time_deltas):
         """(A, Q) for arbitrary, unordered time gaps (any shape): one launch of mfgm_leg_transitions on the device for state_dim <= 8,
         torch.linalg.matrix_exp otherwise."""
         if self.state_dim > 8 or not time_deltas.is_cuda:
-            return self._generic_local(time_deltas)
+            return super().transition_statistics_local(time_deltas)
         from .packed import _ptr, _stream
         d = self.state_dim
         td = time_deltas.detach().to(torch.float64).contiguous()
@@ -753,13 +614,15 @@ class LatentExponentiallyGenerated(_GenericKernel):
         return A, Q
 
 
-class Product(_GenericKernel):
+class Product(StationaryKernel):
     """sde_kernel.py:691-826: A = (x) A_i, Pinf = (x) Pinf_i, H = (x) H_i, state_dim = prod d_i.  Only the Product's own jitter is used
     (the children's is ignored, as in the reference, whose Product inherits transition_statistics and initial_covariance).
 
     Q follows the exact-Q rule: with M_i = A_i Pinf_i A_i^T (M_i = Pinf_i exactly for Constant and
     HarmonicOscillator, and for trees of them), Q = (x) Pinf_i - (x) M_i, rewritten as (Pinf_g - M_g) (x) (x)_{i != g} Pinf_i when g is
     the only child with M_g != Pinf_g, and exactly 0 when there is none."""
+
+    _matern_tree = False
 
     def __init__(self, kernels, jitter=0.0):
         kernels = list(kernels)
@@ -840,8 +703,7 @@ class IndependentMultiOutput(Sum):
         return H
 
     def generate_emission_model(self, time_points):
-        H = self._emission_matrix().to(time_points.device)
-        return EmissionModel(H.expand(tuple(time_points.shape) + tuple(H.shape)).contiguous(), constant_matrix=H)
+        return _emission_model(self._emission_matrix(), time_points)
 
 
 class SparseSpatioTemporalKernel(IndependentMultiOutput):
@@ -879,8 +741,7 @@ class SparseSpatioTemporalKernel(IndependentMultiOutput):
     def generate_emission_model(self, time_points):
         """chol(K_zz) @ blockdiag(H_t) [Ms, Ms d_t], the same at every time point."""
         dev = time_points.device
-        H = self.chol_space(dev) @ self._emission_matrix().to(dev)
-        return EmissionModel(H.expand(tuple(time_points.shape) + tuple(H.shape)).contiguous(), constant_matrix=H)
+        return _emission_model(self.chol_space(dev) @ self._emission_matrix().to(dev), time_points)
 
     def spatial_features(self, x):
         """(a [N, Ms], k_s(x, x) - |a|^2 [N]) with a = chol(K_zz)^-1 k_s(Z_s, x): the spatial half of the projection of f(x, t) onto
@@ -1008,8 +869,7 @@ class PiecewiseKernel:
 
     def generate_emission_model(self, time_points):
         """The children's common H, the same at every time point."""
-        h = self._emission_row().to(time_points.device)[None]
-        return EmissionModel(h.expand(tuple(time_points.shape) + (1, self.state_dim)).contiguous(), constant_matrix=h)
+        return _emission_model(self._emission_row()[None], time_points)
 
     # -- the prior state-space model ----------------------------------------------------------------------------------------------------
     def _terms(self):
@@ -1051,33 +911,18 @@ class PiecewiseKernel:
         if self._terms() is None or os.environ.get("VIDP_PIECEWISE_TORCH", "0") == "1":
             return self._state_space_model_torch(t, bs, plan)
         pw, tab = self._terms_struct(t.device)
-        A, off, chol = plan.piecewise_ssm(pw, t)
-        try:
-            plan.check_info()
-        except ArithmeticError as e:
-            raise ArithmeticError(_NOT_PD) from e
-        ssm = _ssm_from_packed(plan, A, off, chol)
-        ssm.batch_shape = bs
+        ssm = _model_from_packed(plan, plan.piecewise_ssm(pw, t), bs)
         ssm._piecewise_tables = tab      # the launch reads them: kept with the model
         return ssm
 
     def _state_space_model_torch(self, t, bs, plan):
-        """The steps of StationaryKernel._state_space_model_wide on the region-selected closed forms."""
-        dev, d = t.device, self.state_dim
+        """StationaryKernel._state_space_model_wide on the region-selected closed forms."""
         A, Q = self.transition_statistics_at(t[:, :-1], t[:, 1:] - t[:, :-1])
-        zero = (Q == 0).all(dim=-1).all(dim=-1)
-        eye = torch.eye(d, dtype=Q.dtype, device=dev)
         try:
-            chol = linalg.cholesky(torch.where(zero[..., None, None], eye, Q))
-            chol0 = linalg.cholesky(self.initial_covariance(t[:, :1]))
+            return _model_from_torch(A, Q, self.state_means(t[:, :-1]), self.initial_mean().to(t.device),
+                                     self.initial_covariance(t[:, :1]), plan, bs)
         except ArithmeticError as e:
             raise ArithmeticError(_NOT_PD) from e
-        chol = torch.where(zero[..., None, None], torch.zeros_like(chol), chol)
-        m = self.state_means(t[:, :-1])
-        off = m - (A @ m[..., None])[..., 0]
-        ssm = StateSpaceModel(torch.zeros((t.shape[0], d), dtype=torch.float64, device=dev), chol0.contiguous(), A, off, chol, plan=plan)
-        ssm.batch_shape = bs
-        return ssm
 
     # -- hyper-parameters as leaves of a torch graph ------------------------------------------------------------------------------------
     def hyperparameter_leaves(self, device="cpu"):
@@ -1088,7 +933,6 @@ class PiecewiseKernel:
         """(tape.TapeSSM, leaves): the prior SSM at the sorted time points [T] (one chain, d <= 8) as a differentiable function of the
         per-region hyper-parameter leaves -- the children's differentiable _parts on all gaps, selected by the region of each
         transition's left end; a region that holds no left end and not the first point gets a gradient of exactly zero."""
-        from . import tape
         t = time_points.reshape(-1)
         dev, d = t.device, self.state_dim
         if leaves is None:
@@ -1103,13 +947,7 @@ class PiecewiseKernel:
             Pi = Pi.expand(d, d)
             A, Qt = (Ai, Qi) if A is None else (torch.where(rl == i, Ai, A), torch.where(rl == i, Qi, Qt))
             Pinf0 = Pi if Pinf0 is None else torch.where(r[0] == i, Pi, Pinf0)
-        jit = self.jitter * torch.eye(d, dtype=torch.float64, device=dev)
-        Q = Qt + jit
-        m = self.state_means(t[:-1])
-        b = m - (A @ m[..., None])[..., 0]
-        cq = torch.zeros_like(Q) if (exact and self.jitter == 0.0) else tape.cholesky(0.5 * (Q + Q.transpose(-1, -2)))
-        mu0 = torch.zeros((1, d), dtype=torch.float64, device=dev)
-        return tape.TapeSSM(mu0, tape.cholesky(Pinf0 + jit)[None], A[None], b[None], cq[None], plan=plan), leaves
+        return _tape_model(A, Qt, exact, Pinf0, self.state_means(t[:-1]), self.initial_mean().to(dev), self.jitter, plan), leaves
 
 
 def _tree_jitter(kernel):
