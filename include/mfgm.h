@@ -550,6 +550,24 @@ typedef struct mfgm_kernel_terms {
 int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_terms* terms, const double* time_deltas, double* A,
                            double* off, double* chol, int* info, void* stream);
 
+/* Score of the log marginal likelihood with respect to the kernel terms' parameters, from the posterior pairwise moments (Fisher's
+ * identity: d/dh log Z = E_post[d/dh log p_h(x)]; the prior log density is a sum over the transitions of terms quadratic in
+ * (x_k, x_k+1)).  x (VEC): the posterior mean MINUS the prior state mean; Sig (SYM): Sigma_tt; Sub (FULL): Sigma_{t+1,t} stored at
+ * node t -- the packed outputs of mfgm_packed_selinv on a factorisation whose right-hand side is the displacement from the prior.
+ * time_deltas: natural [B, T-1], NULL iff T == 1 (then Sub may be NULL too and only the initial state contributes).  With
+ * S = Sigma_k + x_k x_k^T, S' = Sigma_k+1 + x_k+1 x_k+1^T, C = Sigma_{k+1,k} + x_k+1 x_k^T, M = S' - A C^T - C A^T + A S A^T:
+ *   G_Q = 1/2 (Q^-1 M Q^-1 - Q^-1),  G_A = Q^-1 (C - A S),  G_P0 = 1/2 (P0^-1 S_0 P0^-1 - P0^-1),
+ *   d log Z = <G_P0, dP0> + sum_k <G_Q,k, dQ_k> + <G_A,k, dA_k>,
+ * with (A_k, Q_k, P0 = Pinf + jitter I) those of mfgm_packed_kernel_ssm, rebuilt from the same closed forms (they are not read).
+ * score: natural [B, 8, 3, 2], score[b][c][f] = (d/d rate, d/d var) of chain b's log Z with respect to factor f of term c in the
+ * CALLER's order of `terms`; absent slots and a CONSTANT's rate are exact zeros.  A term block whose Q is exactly zero (zero gap,
+ * CONSTANT) contributes nothing; the caller must not pass a HARMONIC-only term without jitter at positive gaps (its dA is not zero
+ * there: no score exists).  *info is set as by mfgm_packed_kernel_ssm when a Q block is neither positive definite nor zero.
+ * ws: the plan workspace (per-lane partials, then a fixed-order sum per chain: no floating-point atomics, two calls give identical
+ * bits).  Returns 1, before any HIP call, for a null argument, d > 8, and whatever terms mfgm_packed_kernel_ssm rejects. */
+int mfgm_packed_kernel_score(const mfgm_plan* plan, const mfgm_kernel_terms* terms, const double* time_deltas, const double* x,
+                             const double* Sig, const double* Sub, double* score, void* ws, int* info, void* stream);
+
 /* A piecewise-stationary kernel (kernels/piecewise_stationary.py `PiecewiseKernel`): nregion - 1 change points c_k cut the time axis
  * into nregion regions, region r(t) = #{c_k <= t} (a point on a change point belongs to the region after it).  All regions share
  * base's structure (nterm, nfactor, offset, kind) and jitter; region r has the rates rate[r], variances var[r] (both indexed as

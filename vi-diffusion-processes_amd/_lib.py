@@ -63,6 +63,7 @@ EXPORTS = {
     "mfgm_packed_linearize_cubic": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_stationary_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_kernel_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
+    "mfgm_packed_kernel_score": (ctypes.c_int, [ctypes.c_void_p] * 10),
     "mfgm_packed_piecewise_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_leg_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_leg_transitions": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long] + [ctypes.c_void_p] * 4),

@@ -34,9 +34,12 @@ int piecewise_ssm_impl(const Plan& P, const KernelTermsDev& kt, const PiecewiseD
     return 0;
 }
 
+}  // namespace
+
 // The caller's terms -> the kernels' form (1 x 1 factors behind the others; src[c][slot] = the caller's factor in that slot), with
-// every structural check of the two entry points.  0, or 1 for a structure the kernels do not take.
-int device_terms(const Plan& P, const mfgm_kernel_terms& in, KernelTermsDev& kt, int (*src)[3]) {
+// every structural check of the entry points that take mfgm_kernel_terms (declared in mfgm_internal.h).  0, or 1 for a structure the
+// kernels do not take.
+int mfgm::device_terms(const Plan& P, const mfgm_kernel_terms& in, KernelTermsDev& kt, int (*src)[3]) {
     if (P.wide || P.d > 8) return 1;
     if (in.nterm < 1 || in.nterm > 8) return 1;
     memset(&kt, 0, sizeof(kt));
@@ -83,7 +86,6 @@ int device_terms(const Plan& P, const mfgm_kernel_terms& in, KernelTermsDev& kt,
     kt.jitter = in.jitter;
     return 0;
 }
-}  // namespace
 
 extern "C" int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_terms* terms, const double* time_deltas, double* A,
                                       double* off, double* chol, int* info, void* stream) {

@@ -78,6 +78,18 @@ class BaseKalmanFilter:
 
     def log_likelihood(self):
         """log p(obs) summed over the batch (kalman_filter.py:184-255)."""
+        return self._log_likelihood_factor()[0]
+
+    def log_likelihood_and_moments(self):
+        """(log_likelihood(), moments, disp): the factorisation of the posterior precision log_likelihood makes has the displacement
+        y - H mu_prior as right-hand side, so one selected inverse on it gives moments = dict(x, Sig, Sub), packed, with
+        x = posterior mean - prior mean -- the centred pairwise moments the hyper-parameter score needs (hyper.py).  disp [B, T, o]
+        is that displacement."""
+        ll, f, disp = self._log_likelihood_factor()
+        pl = self.prior_ssm.plan
+        return ll, pl.selinv(f["L"], f["G"], f["y"], want_sub=True), disp
+
+    def _log_likelihood_factor(self):
         ssm, pl = self.prior_ssm, self.prior_ssm.plan
         D, S, pr = self._post_precision()
         mu_p = pl.unpack(VEC, ssm._posterior_packed()["s"]["x"])
@@ -91,7 +103,7 @@ class BaseKalmanFilter:
         pl.check_info()
         term2 = 0.5 * f["quad"]
         term3 = -pr["sumlogchol"] - f["logdet"] + 0.5 * self._log_det_observation_precision
-        return (cst + term1 + term2 + term3).sum()
+        return (cst + term1 + term2 + term3).sum(), f, disp
 
     # defaults for the dense variants ---------------------------------------------------------------------
     def _num_data(self):

@@ -152,6 +152,32 @@ class StationaryKernel:
         (order, lam, var), = self._components()
         return [[(order, float(lam), float(var))]]
 
+    def _terms_t(self, leaves):
+        """_terms() with rate and var as torch expressions of hyperparameter_leaves() (its differentiable twin): what carries the
+        device's score with respect to (rate, var) (mfgm_packed_kernel_score) back to the leaves."""
+        (order, lam, var), = self._components_t(leaves)
+        return [[(order, lam, var)]]
+
+    # the names of the positive scalar hyper-parameters, in the order of hyperparameter_leaves()
+    _hyper_names = ()
+
+    def hyperparameter_values(self):
+        """The current hyper-parameters as floats, in the structure of hyperparameter_leaves() (a dict, or a list of dicts for the
+        children of a Sum / Product): the inverse of assign_hyperparameters."""
+        return {n: getattr(self, n) for n in self._hyper_names}
+
+    def assign_hyperparameters(self, values):
+        """Write hyper-parameters (the structure of hyperparameter_leaves(); floats or 0-dim tensors) back into the kernel, under the
+        constructors' validation: a non-positive lengthscale, variance, period, decay or diffusion raises ValueError."""
+        if set(values) != set(self._hyper_names):
+            raise ValueError(f"{type(self).__name__} takes the hyper-parameters {self._hyper_names}, got {tuple(values)}")
+        vals = {n: float(values[n]) for n in self._hyper_names}
+        for n, v in vals.items():
+            if not (v > 0.0 and math.isfinite(v)):
+                raise ValueError(f"{n} must be positive, got {v}")
+        for n, v in vals.items():
+            setattr(self, n, v)
+
     @property
     def feedback_matrix(self):
         (order, lam, _), = self._components()
@@ -297,6 +323,7 @@ def _check(lengthscale, variance):
 class Matern12(StationaryKernel):
     """matern.py:27-127."""
     state_dim = 1
+    _hyper_names = ("lengthscale", "variance")
 
     def __init__(self, lengthscale, variance, output_dim=1, jitter=0.0):
         super().__init__(output_dim, jitter)
@@ -317,6 +344,7 @@ class Matern12(StationaryKernel):
 class OrnsteinUhlenbeck(StationaryKernel):
     """matern.py:130-234: decay lambda, diffusion q, Pinf = q / (2 lambda)."""
     state_dim = 1
+    _hyper_names = ("decay", "diffusion")
 
     def __init__(self, decay, diffusion, output_dim=1, jitter=0.0):
         super().__init__(output_dim, jitter)
@@ -337,6 +365,7 @@ class OrnsteinUhlenbeck(StationaryKernel):
 class Matern32(StationaryKernel):
     """matern.py:237-373."""
     state_dim = 2
+    _hyper_names = ("lengthscale", "variance")
 
     def __init__(self, lengthscale, variance, output_dim=1, jitter=0.0):
         super().__init__(output_dim, jitter)
@@ -357,6 +386,7 @@ class Matern32(StationaryKernel):
 class Matern52(StationaryKernel):
     """matern.py:376-520."""
     state_dim = 3
+    _hyper_names = ("lengthscale", "variance")
 
     def __init__(self, lengthscale, variance, output_dim=1, jitter=0.0):
         super().__init__(output_dim, jitter)
@@ -372,6 +402,21 @@ class Matern52(StationaryKernel):
 
     def _components_t(self, leaves):
         return [(3, math.sqrt(5.0) / leaves["lengthscale"], leaves["variance"])]
+
+
+def _assign_children(kernels, values):
+    """assign_hyperparameters of a Sum / Product: one entry of `values` per child; nothing is written unless every child accepts."""
+    values = list(values)
+    if len(values) != len(kernels):
+        raise ValueError(f"expected hyper-parameters for {len(kernels)} child kernels, got {len(values)}")
+    before = [k.hyperparameter_values() for k in kernels]
+    try:
+        for k, v in zip(kernels, values):
+            k.assign_hyperparameters(v)
+    except Exception:
+        for k, v in zip(kernels, before):
+            k.assign_hyperparameters(v)
+        raise
 
 
 class Sum(StationaryKernel):
@@ -417,6 +462,21 @@ class Sum(StationaryKernel):
             out.extend(t)
         return out
 
+    def _terms_t(self, leaves):
+        out = []
+        for k, lv in zip(self.kernels, leaves):
+            t = k._terms_t(lv)
+            if t is None:
+                return None
+            out.extend(t)
+        return out
+
+    def hyperparameter_values(self):
+        return [k.hyperparameter_values() for k in self.kernels]
+
+    def assign_hyperparameters(self, values):
+        _assign_children(self.kernels, values)
+
     @property
     def feedback_matrix(self):
         return torch.block_diag(*[k.feedback_matrix for k in self.kernels])
@@ -454,6 +514,7 @@ class HarmonicOscillator(StationaryKernel):
     Pinf = variance I, H = [1, 0], Q = 0 (+ jitter)."""
     state_dim = 2
     _matern_tree = False
+    _hyper_names = ("variance", "period")
 
     def __init__(self, variance, period, output_dim=1, jitter=0.0):
         super().__init__(output_dim, jitter)
@@ -484,12 +545,16 @@ class HarmonicOscillator(StationaryKernel):
     def _terms(self):
         return [[(_lib.FACTOR_HARMONIC, 2.0 * math.pi / self.period, self.variance)]]
 
+    def _terms_t(self, leaves):
+        return [[(_lib.FACTOR_HARMONIC, 2.0 * math.pi / leaves["period"], leaves["variance"])]]
+
 
 class Constant(StationaryKernel):
     """constant.py:28-153: k(tau) = variance; A = [[1]], Pinf = [[variance]], H = [1], Q = 0 (+ jitter).  feedback_matrix is zero, as in
     the reference code (its docstring says [[1]])."""
     state_dim = 1
     _matern_tree = False
+    _hyper_names = ("variance",)
 
     def __init__(self, variance, output_dim=1, jitter=0.0):
         super().__init__(output_dim, jitter)
@@ -511,6 +576,9 @@ class Constant(StationaryKernel):
 
     def _terms(self):
         return [[(_lib.FACTOR_CONSTANT, 0.0, self.variance)]]
+
+    def _terms_t(self, leaves):
+        return [[(_lib.FACTOR_CONSTANT, torch.zeros((), dtype=torch.float64, device=leaves["variance"].device), leaves["variance"])]]
 
 
 class LatentExponentiallyGenerated(StationaryKernel):
@@ -571,6 +639,26 @@ class LatentExponentiallyGenerated(StationaryKernel):
 
     def _terms(self):
         return None
+
+    def _terms_t(self, leaves):
+        return None
+
+    def hyperparameter_values(self):
+        """{"N", "R"}: copies of the two matrices (CPU fp64 tensors)."""
+        return {"N": self.N.clone(), "R": self.R.clone()}
+
+    def assign_hyperparameters(self, values):
+        """N and R as [d, d] tensors (any values: the dynamics are unconstrained)."""
+        if set(values) != {"N", "R"}:
+            raise ValueError(f"LatentExponentiallyGenerated takes the hyper-parameters ('N', 'R'), got {tuple(values)}")
+        N = torch.as_tensor(values["N"], dtype=torch.float64).detach().cpu()
+        R = torch.as_tensor(values["R"], dtype=torch.float64).detach().cpu()
+        d = self.state_dim
+        if tuple(N.shape) != (d, d) or tuple(R.shape) != (d, d):
+            raise ValueError(f"N and R must be [{d}, {d}], got {tuple(N.shape)} and {tuple(R.shape)}")
+        if not (bool(torch.isfinite(N).all()) and bool(torch.isfinite(R).all())):
+            raise ValueError("N and R must be finite")
+        self.N, self.R = N.clone(), R.clone()
 
     def _spec(self):
         """mfgm_leg_spec of this kernel: F formed here, in fp64."""
@@ -682,6 +770,21 @@ class Product(StationaryKernel):
                 return None     # a Sum child: not a product of primitive factors
             factors.extend(t[0])
         return [factors] if len(factors) <= 3 else None
+
+    def _terms_t(self, leaves):
+        factors = []
+        for k, lv in zip(self.kernels, leaves):
+            t = k._terms_t(lv)
+            if t is None or len(t) != 1:
+                return None
+            factors.extend(t[0])
+        return [factors] if len(factors) <= 3 else None
+
+    def hyperparameter_values(self):
+        return [k.hyperparameter_values() for k in self.kernels]
+
+    def assign_hyperparameters(self, values):
+        _assign_children(self.kernels, values)
 
 
 class IndependentMultiOutput(Sum):

@@ -319,6 +319,18 @@ class Plan:
                                                    _ptr(self.info), _stream()), "mfgm_packed_kernel_ssm")
         return A, off, chol
 
+    def kernel_score(self, terms, time_deltas, x, Sig, Sub):
+        """Score of the log marginal likelihood with respect to the kernel terms' (rate, var) from the posterior pairwise moments
+        (mfgm_packed_kernel_score): x packed VEC, the posterior mean MINUS the prior state mean, Sig packed SYM, Sub packed FULL
+        (Sigma_{t+1,t}), as `selinv(..., want_sub=True)` returns them; time_deltas natural [B, T-1] (None when T == 1).  Returns the
+        natural device tensor [B, 8, 3, 2]: (d/d rate, d/d var) per chain, term and factor slot in the order of `terms`; absent slots
+        are exact zeros.  Deterministic: two calls give identical bits."""
+        td = time_deltas.contiguous() if time_deltas is not None else None
+        score = torch.empty((self.B, 8, 3, 2), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.mfgm_packed_kernel_score(self.h, ctypes.byref(terms), _ptr(td), _ptr(x), _ptr(Sig), _ptr(Sub), _ptr(score),
+                                                     _ptr(self.ws), _ptr(self.info), _stream()), "mfgm_packed_kernel_score")
+        return score
+
     def piecewise_ssm(self, pw, time_points):
         """Piecewise-stationary kernel (_lib.PiecewiseTerms, its tables on the device) -> packed SSM parameters (A, off, chol);
         time_points natural [B, T], one sorted grid per chain."""

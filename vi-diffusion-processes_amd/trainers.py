@@ -451,3 +451,82 @@ class VIMarkovGPTrainer:
                 logger.info("Model successfully optimized!!!")
                 break
         return elbo_vals, nlpd_vals, rmse_vals, self.prior_params
+
+
+class KernelHyperTrainer:
+    """Learn a GP model's kernel hyper-parameters by Adam on its negative log marginal likelihood -- what the reference's GPR scripts
+    and notebooks do with `Adam.minimize(model.loss, model.trainable_variables)` -- for GaussianProcessRegression and the sites models
+    (CVIGaussianProcess, PowerExpectationPropagation).  The gradient is the model's log_likelihood_and_grad() (one factorisation, one
+    selected inverse, one score pass: hyper.py).
+
+    Adam (tf defaults, `_Adam`) runs on unconstrained values: softplus^-1 of the positive scalars (gpflow's default `positive()`;
+    transform="log" is the other choice), the identity for the LEG kernel's N and R.  learn_noise=True (GPR with a scalar
+    chol_obs_covariance) also learns sigma^2 = chol_obs_covariance^2.
+
+    Single process only: the gradients are NOT summed over ranks (the helpers of the SDE trainers above are not wired in)."""
+
+    def __init__(self, model, lr=0.01, learn_noise=False, transform="softplus"):
+        from . import hyper
+        if transform not in hyper.TRANSFORMS:
+            raise ValueError(f"transform must be one of {tuple(hyper.TRANSFORMS)}, got {transform!r}")
+        self.model = model
+        self.kernel = model._kernel
+        hyper.check_supported(self.kernel)
+        self.learn_noise = bool(learn_noise)
+        if self.learn_noise:
+            chol = getattr(model, "_chol_obs_covariance", None)
+            if chol is None or tuple(chol.shape) != (1, 1) or float(chol[0, 0]) == 0.0:
+                raise ValueError("learn_noise needs a model with a non-zero scalar chol_obs_covariance")
+        self.transform = transform
+        self._fwd, self._inv, self._jac = hyper.TRANSFORMS[transform]
+        self._like = self.kernel.hyperparameter_values()
+        self._adam = _Adam(lr, len(hyper.flatten(self._like)) + (1 if self.learn_noise else 0))
+        self.history = []        # one dict(loss, hyperparameters[, noise_variance]) per step: the state BEFORE the step
+
+    def _noise_variance(self):
+        return float(self.model._chol_obs_covariance[0, 0]) ** 2
+
+    def step(self):
+        """One Adam step; returns the loss (negative log marginal likelihood) BEFORE the step as a float."""
+        import numpy as np
+        from . import hyper
+        out = self.model.log_likelihood_and_grad()
+        loss = -float(out[0])
+        values = hyper.flatten(self.kernel.hyperparameter_values())
+        grads = hyper.flatten(out[1])
+        rec = dict(loss=loss, hyperparameters=self.kernel.hyperparameter_values())
+        if self.learn_noise:
+            values, grads = values + [self._noise_variance()], grads + [out[2]]
+            rec["noise_variance"] = values[-1]
+        self.history.append(rec)
+        # to the unconstrained values u: d loss / du = -(d ll / dx) dx/du
+        us, gus, matrix = [], [], []
+        for x, g in zip(values, grads):
+            if torch.is_tensor(x) and x.dim() > 0:       # LEG's N, R: unconstrained as they are
+                us.append(x.numpy().copy())
+                gus.append(-g.numpy())
+                matrix.append(True)
+            else:
+                u = self._inv(float(x))
+                us.append(u)
+                gus.append(-float(g) * self._jac(u))
+                matrix.append(False)
+        new = self._adam.step(us, gus)
+        vals = [torch.from_numpy(np.asarray(u)) if m else self._fwd(float(u)) for u, m in zip(new, matrix)]
+        if self.learn_noise:
+            s2 = vals.pop()
+            self.model._chol_obs_covariance = torch.full_like(self.model._chol_obs_covariance, math.sqrt(s2))
+        self.kernel.assign_hyperparameters(hyper.unflatten(self._like, vals))
+        if hasattr(self.model, "kernel_changed"):
+            self.model.kernel_changed()         # (a GaussianProcessRegression builds its prior from the kernel at every call)
+        return loss
+
+    def fit(self, n_steps, site_updates=0):
+        """n_steps Adam steps, each after `site_updates` calls of model.update_sites() (the alternation of the reference's CVI
+        notebooks); returns the list of the steps' losses."""
+        losses = []
+        for _ in range(int(n_steps)):
+            for _ in range(int(site_updates)):
+                self.model.update_sites()
+            losses.append(self.step())
+        return losses

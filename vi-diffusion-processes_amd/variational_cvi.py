@@ -57,6 +57,30 @@ class GaussianProcessRegression:
     def log_likelihood(self):
         return self._kalman.log_likelihood()
 
+    def log_likelihood_and_grad(self):
+        """(ll, kernel_grads, noise_grad): log_likelihood() -- bit for bit, the same launches in the same order -- with its gradient
+        with respect to the kernel's hyper-parameters (the structure of kernel.hyperparameter_leaves(), 0-dim CPU fp64 tensors; N and
+        R matrices for the LEG kernel) and to the scalar observation noise sigma^2 = chol_obs_covariance^2 (None when that is zero).
+        One factorisation, one selected inverse and one score pass (hyper.py); the chains of a batch share the
+        hyper-parameters, so their scores are summed."""
+        from . import hyper
+        hyper.precheck(self._kernel)        # before the prior is built: a refused kernel launches nothing
+        kf = self._kalman
+        ll, grads, moments, disp = hyper.kernel_score(self._kernel, kf, self._time_points)
+        chol = self._chol_obs_covariance
+        if tuple(chol.shape) != (1, 1) or float(chol[0, 0]) == 0.0:
+            return ll, grads, None
+        # d ll / d sigma^2 = 1/2 sum [((y - m_f)^2 + v_f) / sigma^4 - 1 / sigma^2] from the posterior f-marginals
+        pl = kf.prior_ssm.plan
+        H = kf._H()
+        x = pl.unpack(VEC, moments["x"])
+        Sig = pl.unpack(SYM, moments["Sig"])
+        r = disp - torch.einsum("...ij,...j->...i", H, x)
+        v = torch.einsum("...ij,...jk,...lk->...il", H, Sig, H)[..., 0, 0]
+        s2 = chol[0, 0] ** 2
+        noise_grad = 0.5 * (((r[..., 0] ** 2 + v) / (s2 * s2)).sum() - r[..., 0].numel() / s2)
+        return ll, grads, noise_grad.detach().to("cpu", torch.float64)
+
     @property
     def posterior_state_space_model(self):
         return self._kalman.posterior_state_space_model()
@@ -142,6 +166,25 @@ class GaussianProcessWithSitesBase:
 
     def loss(self):
         return -self.log_likelihood()
+
+    def log_likelihood_and_grad(self):
+        """(ll, kernel_grads): the marginal likelihood of the model whose likelihood terms are the current Gaussian sites (what
+        CVIGaussianProcess.elbo() returns, here through the unfused factorisation) and its gradient with respect to the kernel's
+        hyper-parameters at FIXED sites, in the structure of kernel.hyperparameter_leaves() (CPU fp64 tensors): one factorisation,
+        one selected inverse and one score pass (hyper.py)."""
+        from . import hyper
+        hyper.precheck(self._kernel)        # before the prior is built: a refused kernel launches nothing
+        ll, grads, _, _ = hyper.kernel_score(self._kernel, self.posterior_kalman, self._time_points)
+        return ll, grads
+
+    def kernel_changed(self):
+        """Drop everything derived from the kernel's hyper-parameters -- the prior state-space model (with the fused calls' caches and
+        scratch, which hang on it) and the emission model -- after kernel.assign_hyperparameters(); the sites stay."""
+        self._dist_p = None
+        self._em = None
+        self._cache = None
+        if getattr(self, "_norm_p", None) is not None:      # PowerExpectationPropagation's cached prior normaliser
+            self._norm_p = None
 
     def predict_f_at_data(self):
         """posterior.predict_f(self.time_points): at the conditioning points this is (H mu, H Sigma H^T) of dist_q."""
