@@ -966,6 +966,40 @@ int mfgm_st_predict_kl(const mfgm_st_data* data, const double* mu, const double*
 int mfgm_st_site_update_q(const mfgm_st_data* data, const double* g1, const double* g2, double lr, double* nat1, double* nat2q,
                           void* stream);
 
+/* ---- linear-readout likelihoods of the diffusion models (CVISitesSSM / CVISitesSDE; csrc/mfgm_readout.h) -------------------------------
+ * p(y_i | x_i) = prod_j p_j(y_ij | f_ij),  f_ij = h_j^T x_i + c_j,  j = 0 .. o-1:  H [o, d] row-major, offset c [o], one scalar factor per
+ * output:  kind MFGM_LIK_GAUSSIAN (param = variance s^2 > 0), MFGM_LIK_BERNOULLI (param = jitter in [0, 1/2)) or MFGM_LIK_POISSON
+ * (param = bin size > 0).  Contract (fp64), per observation i with marginal q(x_i) = N(mu, Sigma) and output j:
+ *      m_j = h_j^T mu + c_j,   v_j = h_j^T Sigma h_j,   (ve_j, dm_j, dv_j) = (VE, dVE/dmu, dVE/dv) of mfgm_scalar_lik at (m_j, v_j, y_ij);
+ *      Gaussian:  ve = -1/2 log(2 pi s^2) - 1/2 ((y - m)^2 + v) / s^2,  dm = (y - m) / s^2,  dv = -1/2 / s^2;
+ *      a NaN y_ij (output j not observed at i) gives ve_j = dm_j = dv_j = 0;
+ *      VE_i = sum_j ve_j,   g2_i = sum_j dv_j h_j h_j^T,   g1_i = sum_j h_j (dm_j - 2 dv_j h_j^T mu)     (h_j^T mu, without the offset):
+ * the gradient of VE_i with respect to the expectation parameters (mu, Sigma + mu mu^T) of the state.
+ * y [n, o] row-major and node_ids [n] (b T + t, int64) are device arrays; lane-per-segment plans only (d <= 8), B T < 2^32.
+ *
+ * mfgm_readout_site_update: update_data_sites (variational_cvi_sde.py:301-317) at the listed nodes in one launch -- the contract of
+ *   mfgm_site_update_pair with the gradient made inside.  The marginals are read from the packed mu (VEC) / Sig (SYM) at node_ids[i]
+ *   (gathered = 0) or from natural mu [n, d] / Sig [n, d, d] in observation order (gathered = 1, lower triangle read); then
+ *   sites <- (1 - lr) sites + lr g for sites_vec [n, d] and sites_sym [n, d, d] (element-wise, both triangles written), and
+ *   theta_lin (VEC) / theta_diag (SYM) += new - old at the node.  The scatter is a plain read-modify-write: the node ids of one call
+ *   must be distinct.
+ * mfgm_readout_obs_ve: sum_i VE_i per trajectory as nb = ceil(n_per / 256) fixed-order partial sums, ve [B, nb]; node_ids / y are
+ *   trajectory-major with n_per observations each; the gathered marginals go to out_mu [B n_per, d] / out_cov [B n_per, d, d] when not
+ *   NULL (the contract and launch shape of mfgm_mvn_obs_ve).
+ * One lane per observation; no atomics, no allocation, no host synchronisation (graph-capturable).  Both return 1 for a wide plan,
+ * o outside 1 .. 8, readout.d != the plan's d, an unknown kind, a parameter out of range, lr outside [0, 1], gathered other than 0 / 1,
+ * or a missing pointer when there is an observation; n = 0 (n_per = 0) is a no-op that returns 0. */
+typedef struct mfgm_readout {
+    int o, d, kind[8];
+    double param[8], offset[8], H[64];
+} mfgm_readout;
+int mfgm_readout_site_update(const mfgm_plan* plan, const mfgm_readout* readout, const double* mu, const double* Sig, int gathered,
+                             const long long* node_ids, int n, const double* y, double* theta_lin, double* theta_diag,
+                             double* sites_vec, double* sites_sym, double lr, void* stream);
+int mfgm_readout_obs_ve(const mfgm_plan* plan, const mfgm_readout* readout, const double* mu, const double* Sig,
+                        const long long* node_ids, int n_per, const double* y, double* out_mu, double* out_cov, double* ve,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,9 @@ EXPORTS = {
                                 + [ctypes.c_void_p] * 9),
     "mfgm_st_predict_kl": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_double] * 2 + [ctypes.c_void_p] * 5),
     "mfgm_st_site_update_q": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
+    "mfgm_readout_site_update": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5
+                                 + [ctypes.c_double, ctypes.c_void_p]),
+    "mfgm_readout_obs_ve": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] + [ctypes.c_void_p] * 5),
 }
 
 
@@ -206,6 +209,12 @@ class KfSites(ctypes.Structure):
     """mfgm_kf_sites (include/mfgm.h)."""
     _fields_ = [("H", ctypes.c_double * 32), ("o", ctypes.c_int), ("site_batch", ctypes.c_int), ("nat1", ctypes.c_void_p),
                 ("nat2", ctypes.c_void_p), ("Hmu", ctypes.c_void_p)]
+
+
+class Readout(ctypes.Structure):
+    """mfgm_readout (include/mfgm.h)."""
+    _fields_ = [("o", ctypes.c_int), ("d", ctypes.c_int), ("kind", ctypes.c_int * 8), ("param", ctypes.c_double * 8),
+                ("offset", ctypes.c_double * 8), ("H", ctypes.c_double * 64)]
 
 
 class KernelSpec(ctypes.Structure):

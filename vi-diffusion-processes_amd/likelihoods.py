@@ -7,6 +7,9 @@ the gathered observation nodes.
 
 The scalar non-Gaussian likelihoods of the CVI models (Bernoulli, Poisson; gpflow.likelihoods) follow at the end: 20-point
 Gauss-Hermite variational expectations and their site gradients, natively in one launch (mfgm_scalar_lik).
+
+LinearReadout, last, lets the diffusion models see their state through f = H x + c with one of these scalar likelihoods per output
+(DESIGN.md section 19).
 """
 import math
 import weakref
@@ -414,3 +417,160 @@ class PEPGaussian(PEPScalarLikelihood):
             return super().grad_log_expected_density(Fmu, Fvar, Y, alpha)
         lz, d1, d2 = self._terms(Fmu, Fvar, Y, alpha)
         return lz[..., 0], (d1, d2)
+
+
+# ---- linear readout: a diffusion observed through f = H x + c with one scalar likelihood per output ------------------------------------
+class LinearReadout:
+    """p(y_i | x_i) = prod_j p_j(y_ij | f_ij),  f_ij = h_j^T x_i + c_j: the state of a diffusion model (CVISitesSSM, CVISitesSDE,
+    CVISitesSDEQuadrature) seen through `emission` H [o, d] (1 <= o <= 8) and `offset` c [o] (default 0), with one scalar likelihood per
+    output -- `likelihoods` is one likelihood shared by all outputs or a sequence of o of them.  A NaN entry of y says that the output was
+    not observed there: it contributes exactly 0 to the variational expectation and to the gradients.
+
+    Contract (include/mfgm.h, mfgm_readout), per observation with marginal N(mu, Sigma), m_j = h_j^T mu + c_j, v_j = h_j^T Sigma h_j and
+    (ve_j, dm_j, dv_j) the scalar likelihood's variational expectation and its derivatives at (m_j, v_j):
+        VE = sum_j ve_j,   g2 = sum_j dv_j h_j h_j^T,   g1 = sum_j h_j (dm_j - 2 dv_j h_j^T mu)
+    (the gradient with respect to the expectation parameters of the state; the offset does not enter g1 through mu).
+
+    Gaussian, Bernoulli and Poisson factors are the native kinds: the diffusion models then make the data-site update and the
+    variational expectations in one HIP launch each (Plan.readout_site_update / readout_obs_ve).  The methods
+    below are the torch route: any ScalarQuadratureLikelihood, any device, differentiable.  H and c are fixed (not trainable)."""
+
+    uniform_site_gradient = False      # the site gradient depends on q: the models keep the dense per-node arrays
+
+    def __init__(self, emission, likelihoods, offset=None):
+        H = torch.as_tensor(emission, dtype=torch.float64).detach()
+        if H.dim() != 2 or not 1 <= H.shape[0] <= 8:
+            raise ValueError("emission must be [o, d] with 1 <= o <= 8")
+        self.obs_dim, self.state_dim = int(H.shape[0]), int(H.shape[1])
+        c = torch.zeros(self.obs_dim, dtype=torch.float64) if offset is None else torch.as_tensor(offset, dtype=torch.float64).detach()
+        if tuple(c.shape) != (self.obs_dim,):
+            raise ValueError("offset must be [o]")
+        self.emission, self.offset = H.contiguous(), c.to(H.device).contiguous()
+        if isinstance(likelihoods, (list, tuple)):
+            if len(likelihoods) != self.obs_dim:
+                raise ValueError("one likelihood per output (or a single shared one)")
+            self.likelihoods = list(likelihoods)
+        else:
+            self.likelihoods = [likelihoods] * self.obs_dim
+        for b in self.likelihoods:
+            if not isinstance(b, (Gaussian, ScalarQuadratureLikelihood)):
+                raise TypeError("the factors of a LinearReadout are Gaussian or ScalarQuadratureLikelihood (Bernoulli, Poisson, ...)")
+        self._dev_cache, self._desc = {}, None
+
+    # ---- native description ----------------------------------------------------------------------------------------------------------
+    @property
+    def native_kinds(self):
+        """True when every factor is one of the kinds the HIP kernels know (Gaussian, Bernoulli, Poisson themselves, not subclasses)."""
+        return all(type(b) in (Gaussian, Bernoulli, Poisson) for b in self.likelihoods) and self.state_dim <= 8
+
+    def descriptor(self):
+        """_lib.Readout of the emission, the offset and the factors' current parameters (native kinds only); rebuilt when a parameter
+        has changed."""
+        from . import _lib
+        if not self.native_kinds:
+            raise TypeError("a LinearReadout with a factor other than Gaussian, Bernoulli or Poisson (or d > 8) has no native description")
+        key = tuple((type(b), b.variance if type(b) is Gaussian else b.param) for b in self.likelihoods)
+        if self._desc is not None and self._desc[0] == key:
+            return self._desc[1]
+        rd = _lib.Readout()
+        rd.o, rd.d = self.obs_dim, self.state_dim
+        for j, b in enumerate(self.likelihoods):
+            if type(b) is Gaussian:
+                rd.kind[j], rd.param[j] = _lib.LIK_GAUSSIAN, b.variance
+            else:
+                rd.kind[j], rd.param[j] = b.kind, b.param
+            rd.offset[j] = float(self.offset[j])
+        for k, v in enumerate(self.emission.reshape(-1).tolist()):
+            rd.H[k] = v
+        self._desc = (key, rd)
+        return rd
+
+    def _Hc(self, like):
+        """(H, c) on `like`'s device (made once per device)."""
+        key = str(like.device)
+        r = self._dev_cache.get(key)
+        if r is None:
+            r = self._dev_cache[key] = (self.emission.to(like.device), self.offset.to(like.device))
+        return r
+
+    # ---- projections -----------------------------------------------------------------------------------------------------------------
+    def project(self, f_means, f_covariances):
+        """(m, v) [..., n, o]: m_j = h_j^T mu + c_j, v_j = h_j^T Sigma h_j."""
+        H, c = self._Hc(f_means)
+        hm = (f_means[..., None, :] * H).sum(-1)
+        v = ((f_covariances[..., None, :, :] * H[:, None, :]).sum(-1) * H).sum(-1)
+        return hm + c, v
+
+    @staticmethod
+    def _seen(observations):
+        """(mask of the observed entries, y with the others replaced by 0)."""
+        seen = ~torch.isnan(observations)
+        return seen, torch.where(seen, observations, torch.zeros_like(observations))
+
+    def _per_output(self, fn, *cols):
+        """fn(base_j, column j of every tensor as [..., n, 1]) for each output, stacked on a new last axis."""
+        return torch.stack([fn(b, *(t[..., j:j + 1] for t in cols)) for j, b in enumerate(self.likelihoods)], dim=-1)
+
+    # ---- interface of the diffusion models -----------------------------------------------------------------------------------------------
+    def variational_expectations(self, f_means, f_covariances, observations):
+        """E_q log p(y_i | x_i) = sum over the observed outputs of the factors' variational expectations, [..., n] (differentiable)."""
+        m, v = self.project(f_means, f_covariances)
+        seen, y = self._seen(observations)
+        ve = self._per_output(lambda b, mj, vj, yj: b.variational_expectations(mj, vj, yj).reshape(mj.shape[:-1]), m, v, y)
+        return torch.where(seen, ve, torch.zeros_like(ve)).sum(-1)
+
+    @staticmethod
+    def _scalar_derivatives(b, mj, vj, yj):
+        """(dVE/dm, dVE/dv) [..., n, 1] of one factor."""
+        if isinstance(b, Gaussian):
+            return (yj - mj) / b.variance, torch.full_like(vj, -0.5 / b.variance)
+        mj, vj, yj = mj.contiguous(), vj.contiguous(), yj.contiguous()
+        if b._native(mj, vj, yj):
+            _, g1, g2 = b._launch(mj, vj, yj, grads=True)      # (dm - 2 dv m, dv)
+            return g1 + 2.0 * g2 * mj, g2
+        with torch.enable_grad():
+            mu = mj.detach().requires_grad_(True)
+            var = vj.detach().requires_grad_(True)
+            dm, dv = torch.autograd.grad(b._ve_torch(mu, var, yj.detach()).sum(), [mu, var])
+        return dm, dv
+
+    def ve_gradients_expectation(self, f_means, f_covariances, observations):
+        """(g1 [..., n, d], g2 [..., n, d, d]): the gradient of sum_i VE_i with respect to the expectation parameters (mu, Sigma + mu mu^T)
+        of the state."""
+        H, c = self._Hc(f_means)
+        f_means, f_covariances = f_means.detach(), f_covariances.detach()
+        m, v = self.project(f_means, f_covariances)
+        seen, y = self._seen(observations.detach())
+        dm, dv = [], []
+        for j, b in enumerate(self.likelihoods):
+            a, e = self._scalar_derivatives(b, m[..., j:j + 1], v[..., j:j + 1], y[..., j:j + 1])
+            dm.append(a[..., 0])
+            dv.append(e[..., 0])
+        zero = torch.zeros_like(m)
+        dm, dv = torch.where(seen, torch.stack(dm, -1), zero), torch.where(seen, torch.stack(dv, -1), zero)
+        a = dm - 2.0 * dv * (m - c)
+        g1 = (a[..., :, None] * H).sum(-2)
+        g2 = ((dv[..., :, None] * H)[..., :, :, None] * H[:, None, :]).sum(-3)
+        return g1, g2
+
+    # ---- predictions -------------------------------------------------------------------------------------------------------------------
+    def predict_mean_and_var(self, f_means, f_covariances):
+        """Mean and variance of every output, [..., n, o] each (per output the factor's predict_mean_and_var at (m_j, v_j))."""
+        m, v = self.project(f_means, f_covariances)
+        out = [b.predict_mean_and_var(m[..., j:j + 1], v[..., j:j + 1]) for j, b in enumerate(self.likelihoods)]
+        return torch.cat([a for a, _ in out], -1), torch.cat([e for _, e in out], -1)
+
+    def predict_log_density(self, f_means, f_covariances, observations):
+        """log p(y_i) under the marginal, summed over the observed outputs, [..., n]: log N(y; m, v + s^2) for a Gaussian factor, the
+        factor's own predict_log_density otherwise."""
+        m, v = self.project(f_means, f_covariances)
+        seen, y = self._seen(observations)
+
+        def one(b, mj, vj, yj):
+            if isinstance(b, Gaussian):
+                s = vj + b.variance
+                return (-0.5 * torch.log(2.0 * math.pi * s) - 0.5 * (yj - mj) ** 2 / s).sum(-1)
+            return b.predict_log_density(mj, vj, yj)
+
+        lp = self._per_output(one, m, v, y)
+        return torch.where(seen, lp, torch.zeros_like(lp)).sum(-1)

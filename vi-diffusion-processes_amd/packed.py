@@ -259,6 +259,33 @@ class Plan:
                                             _ptr(out_mu), _ptr(out_cov), _ptr(ve), _stream()), "mfgm_mvn_obs_ve")
         return ve.sum(-1)
 
+    def readout_site_update(self, readout, mu, Sig, node_ids, y, theta_lin, theta_diag, sites_vec, sites_sym, lr, gathered=False):
+        """update_data_sites under a linear-readout likelihood at the listed (distinct) nodes in one launch (mfgm_readout_site_update,
+        d <= 8): the site gradient from the marginals (packed mu VEC / Sig SYM, or with gathered=True natural [n, d] / [n, d, d] in
+        observation order), sites <- (1 - lr) sites + lr g in place, theta_lin / theta_diag += new - old.  readout: _lib.Readout;
+        y [n, o]."""
+        for t in (y, sites_vec, sites_sym):
+            assert t.is_contiguous()
+        n = node_ids.numel()
+        assert tuple(sites_vec.shape) == (n, self.d) and tuple(sites_sym.shape) == (n, self.d, self.d) and y.numel() == n * readout.o
+        if gathered:
+            assert mu.is_contiguous() and Sig.is_contiguous() and tuple(mu.shape) == (n, self.d) and tuple(Sig.shape) == (n, self.d, self.d)
+        _lib.check(self.lib.mfgm_readout_site_update(self.h, ctypes.byref(readout), _ptr(mu), _ptr(Sig), int(bool(gathered)),
+                                                     _ptr(node_ids), n, _ptr(y), _ptr(theta_lin), _ptr(theta_diag), _ptr(sites_vec),
+                                                     _ptr(sites_sym), float(lr), _stream()), "mfgm_readout_site_update")
+        for t in (theta_lin, theta_diag, sites_vec, sites_sym):
+            torch.autograd.graph.increment_version(t)      # written behind torch's back
+
+    def readout_obs_ve(self, readout, mu, Sig, node_ids, n_per, y, out_mu=None, out_cov=None, partials=False):
+        """Per-trajectory variational expectations under a linear-readout likelihood at the observation nodes, gathered from the packed
+        marginals in the same launch (mfgm_readout_obs_ve, d <= 8).  y: [B * n_per, o] trajectory-major; returns ve [B] (partials=True:
+        the fixed-order block sums [B, ceil(n_per / 256)])."""
+        assert y.is_contiguous() and node_ids.numel() == self.B * int(n_per) and y.numel() == node_ids.numel() * readout.o
+        ve = torch.empty((self.B, (int(n_per) + 255) // 256), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.mfgm_readout_obs_ve(self.h, ctypes.byref(readout), _ptr(mu), _ptr(Sig), _ptr(node_ids), int(n_per), _ptr(y),
+                                                _ptr(out_mu), _ptr(out_cov), _ptr(ve), _stream()), "mfgm_readout_obs_ve")
+        return ve if partials else ve.sum(-1)
+
     def ssm_to_naturals(self, A, off, chol, precision=False, want_logdet=False, out=None):
         """Packed SSM parameters -> naturals (or precision blocks).  Returns dict(lin, diag, sub, sumlogchol)."""
         out = {} if out is None else out

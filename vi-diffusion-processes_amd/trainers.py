@@ -63,6 +63,8 @@ class _Metrics:
         B, n, d = self.y.shape
         m = pl.gather_nodes(VEC, mu_packed, self.node_ids)
         S = pl.gather_nodes(SYM, Sig_packed, self.node_ids)
+        if hasattr(lik, "project"):
+            return tuple(float(v) for v in self._readout_sums(lik, m, S))
         # likelihood.predict_mean_and_var: y* ~ N(m, S + R)
         R = lik.chol_covariance @ lik.chol_covariance.transpose(-1, -2)
         chol = linalg.cholesky(S + R)
@@ -76,12 +78,25 @@ class _Metrics:
         B, n, d = self.y.shape
         m = pl.gather_nodes(VEC, mu_packed, self.node_ids)
         S = pl.gather_nodes(SYM, Sig_packed, self.node_ids)
+        if hasattr(lik, "project"):
+            return self._readout_sums(lik, m, S)
         R = lik.chol_covariance @ lik.chol_covariance.transpose(-1, -2)
         chol = linalg.cholesky(S + R, check=False)          # (no synchronisation: a failed pivot shows as NaN in the sums)
         z = linalg.solve_lower(chol, self.y.reshape(B * n, d) - m)
         logp = -0.5 * (z * z).sum(-1) - torch.log(torch.diagonal(chol, dim1=-2, dim2=-1)).sum(-1) - 0.5 * d * math.log(2 * math.pi)
         cnt = torch.tensor([float(B * n), float(B * n * d)], dtype=torch.float64, device=m.device)
         return torch.cat([logp.sum().reshape(1), ((m - self.y.reshape(B * n, d)) ** 2).sum().reshape(1), cnt])
+
+    def _readout_sums(self, lik, m, S):
+        """The four sums under a LinearReadout likelihood, a device tensor [4]: log predictive densities of the points (over their
+        observed outputs) and squared errors of the predicted output means at the observed entries (a NaN entry is not counted)."""
+        B, n, o = self.y.shape
+        y = self.y.reshape(B * n, o)
+        logp = lik.predict_log_density(m, S, y)
+        seen = ~torch.isnan(y)
+        err = torch.where(seen, lik.predict_mean_and_var(m, S)[0] - y, torch.zeros_like(y))
+        cnt = torch.tensor([float(B * n)], dtype=torch.float64, device=m.device)
+        return torch.cat([logp.sum().reshape(1), (err * err).sum().reshape(1), cnt, seen.sum().to(torch.float64).reshape(1)])
 
     @staticmethod
     def finish(logp_sum, se_sum, n_points, n_entries):

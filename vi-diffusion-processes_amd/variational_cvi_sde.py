@@ -51,11 +51,19 @@ class CVISitesSSM:
         self.time_grid = torch.as_tensor(time_grid, dtype=torch.float64)
         self.dt = float(self.time_grid[1] - self.time_grid[0])
         self._observations = observations.contiguous()
-        self.B, self.n_obs, self.state_dim = observations.shape
+        # a likelihood that sees the state through a readout (likelihoods.LinearReadout) names the state dimension itself; otherwise every
+        # state coordinate is observed
+        self.B, self.n_obs, self.obs_dim = observations.shape
+        self.state_dim = int(getattr(likelihood, "state_dim", self.obs_dim))
         self.output_dim = self.state_dim
         self.T = int(self.time_grid.numel())
         self.device = observations.device
         self.obs_sites_indices = grid_indices(self.time_grid, obs_times).to(self.device)
+        if hasattr(likelihood, "project") and self.n_obs > 1:
+            # the readout's site update scatters into the posterior naturals with one plain read-modify-write per observation
+            ordered = self.obs_sites_indices.sort(dim=-1).values
+            if bool((ordered[..., 1:] == ordered[..., :-1]).any()):
+                raise ValueError("observation times that repeat within a trajectory are not supported with a LinearReadout likelihood")
         if plan is None:
             # segments aligned with an equally spaced observation grid (packed.aligned_segment_length)
             r0 = aligned_segment_length(self.B, self.T, self.state_dim, observation_period(self.obs_sites_indices))
@@ -221,7 +229,7 @@ class CVISitesSSM:
     def _obs_flat(self):
         # one view object for the model's lifetime: the likelihood keys its gradient cache on the tensor object and its version
         if getattr(self, "_obs_flat_view", None) is None:
-            self._obs_flat_view = self._observations.view(self.B * self.n_obs, self.state_dim)
+            self._obs_flat_view = self._observations.view(self.B * self.n_obs, self.obs_dim)
         return self._obs_flat_view
 
     def _obs_marginals(self):
@@ -230,8 +238,37 @@ class CVISitesSSM:
             self._gather_obs()
         return self.fx_mus_obs, self.fx_covs_obs
 
+    # a LinearReadout likelihood of native kinds: the data-site update and the variational expectations in one launch each
+    # (csrc/mfgm_readout.h; VIDP_NATIVE_READOUT=0: the likelihood's torch route around the gather / scatter kernels)
+    native_readout = os.environ.get("VIDP_NATIVE_READOUT", "1") != "0"
+
+    def _readout_native(self):
+        """The likelihood's kernel descriptor when the native readout route applies, else None."""
+        lik = self.likelihood
+        if not (self.native_readout and self.fused_obs_kernels and self.plan.d <= 8 and hasattr(lik, "project")
+                and getattr(lik, "native_kinds", False) and self._observations.is_cuda and self.data_nat1.is_contiguous()
+                and self.data_nat2.is_contiguous()):
+            return None
+        return lik.descriptor()
+
     def update_data_sites(self, lr: float):
         """theta_data <- (1-lr) theta_data + lr dVE/d(eta) at the current marginals (variational_cvi_sde.py:301-317)."""
+        rd = self._readout_native()
+        if rd is not None:
+            tq = self.full_sites()
+            if self._started:
+                # the marginals are read from the packed arrays of the refresh at the observation nodes (no gather first)
+                q = self._refresh(want_marginals=True)
+                self.plan.readout_site_update(rd, q["mu"], q["Sig"], self.obs_node_ids, self._obs_flat(), tq.lin, tq.diag, self.data_nat1,
+                                              self.data_nat2, lr)
+            else:
+                # before the first update the marginals are those of the initial posterior path, gathered at construction
+                self.plan.readout_site_update(rd, self.fx_mus_obs, self.fx_covs_obs, self.obs_node_ids, self._obs_flat(), tq.lin, tq.diag,
+                                              self.data_nat1, self.data_nat2, lr, gathered=True)
+            self._started = True
+            self._q = None
+            self._obs_fresh = False
+            return
         mu_o, cov_o = self._obs_marginals()
         self._started = True      # before the first update the marginals are those of the initial posterior path
         g1, g2 = self.likelihood.ve_gradients_expectation(mu_o, cov_o, self._obs_flat())
@@ -285,6 +322,14 @@ class CVISitesSSM:
                                       lik.ve_constant, out_mu=self.fx_mus_obs, out_cov=self.fx_covs_obs)
             self._obs_fresh = True
             return ve
+        rd = self._readout_native()
+        if rd is not None:
+            # projections, per-output expectations and per-trajectory sum in one launch (it also refreshes the gathered marginals)
+            q = self._refresh(want_marginals=True)
+            ve = self.plan.readout_obs_ve(rd, q["mu"], q["Sig"], self.obs_node_ids, self.n_obs, self._obs_flat(), out_mu=self.fx_mus_obs,
+                                          out_cov=self.fx_covs_obs)
+            self._obs_fresh = True
+            return ve
         if self._q is None or not getattr(self, "_obs_fresh", False):
             self._gather_obs()
         ve = lik.variational_expectations(self.fx_mus_obs, self.fx_covs_obs, self._obs_flat())
@@ -317,7 +362,7 @@ class CVISitesSDE(CVISitesSSM):
     def __init__(self, prior_sde, time_grid, input_data, likelihood, prior_initial_state=None, initial_posterior_path=None,
                  stabilize_ssm=True, clip_state_transitions=(-1.0, 1.0), plan=None):
         self.prior_sde = prior_sde
-        d = input_data[1].shape[-1]
+        d = int(getattr(likelihood, "state_dim", input_data[1].shape[-1]))
         if prior_initial_state is None:
             q = prior_sde.q.cpu().numpy()
             prior_initial_state = (torch.zeros(d, dtype=torch.float64).numpy(), q * (torch.ones((d, d), dtype=torch.float64).numpy()))
@@ -953,7 +998,7 @@ class CVISitesSDEQuadrature(CVISitesSSM):
     def __init__(self, prior_sde, time_grid, input_data, likelihood, prior_initial_state=None, initial_posterior_path=None,
                  stabilize_ssm=True, clip_state_transitions=(-1.0, 1.0), plan=None):
         self.prior_sde = prior_sde
-        d = input_data[1].shape[-1]
+        d = int(getattr(likelihood, "state_dim", input_data[1].shape[-1]))
         if prior_initial_state is None:
             q = prior_sde.q.cpu().numpy()
             prior_initial_state = (torch.zeros(d, dtype=torch.float64).numpy(), q * (torch.ones((d, d), dtype=torch.float64).numpy()))
