@@ -1567,7 +1567,10 @@ def test_cvi_dp_pipelined_steps_equal_unpipelined(amd, rng, streams):
     mfgm_cq_factor_pipelined: as the second wavefront of the forward sweep's workgroups, k_forward_reduce_cq, or on a second stream,
     k_reduce_cq_lean) against the same model with it switched off: ELBO after every step of a loop that keeps its
     learning rates (records are consumed), changes them (a record is dropped), re-linearises, evaluates the ELBO twice and updates
-    the Girsanov sites twice in a row -- equal to rounding of the last bit (the record holds the numbers the reduce would write)."""
+    the Girsanov sites twice in a row -- equal to rounding of the last bit (the record holds the numbers the reduce would write).
+    Then three ways of invalidating a record that a classic_elbo has just made, each followed by two ordinary steps: "x" another
+    factorisation on the model's plan, "a" a new tensor assigned to data_nat1, "i" data_nat1 edited in place through torch.  The next
+    update_data_sites must not take the record over."""
     import torch
     from vidp_amd import sde as gsde
     from vidp_amd.likelihoods import MultivariateGaussian
@@ -1588,21 +1591,40 @@ def test_cvi_dp_pipelined_steps_equal_unpipelined(amd, rng, streams):
     b.pipe_two_streams = streams          # the reduce made ahead: second wavefront of the forward kernel / kernel of its own on a second stream
     assert b._cq_state() is not None
     prog = [("s", 0.5, 0.1)] * 4 + [("s", 0.3, 0.1)] * 2 + [("r",)] + [("s", 0.3, 0.2)] * 2 + [("e",), ("g", 0.1), ("s", 0.3, 0.2), ("s", 0.3, 0.2)]
-    got, want, used = [], [], 0
-    for op in prog:
+    more = [("x",), ("s", 0.3, 0.2), ("s", 0.3, 0.2), ("a",), ("s", 0.3, 0.2), ("s", 0.3, 0.2), ("i",), ("s", 0.3, 0.2), ("s", 0.3, 0.2)]
+    got, want, used, held = [], [], None, None
+    for k, op in enumerate(prog + more):
+        if k == len(prog):
+            used = b._ahead.consumed
         for m, out in ((a, want), (b, got)):
             if op[0] == "s":
                 m.update_data_sites(op[1])
-                if m is b and b._pre is not None and b._pre.get("armed"):
-                    used += 1
+                if m is b and held is not None:
+                    assert b._ahead.consumed == held      # the record made before the "x" / "a" / "i" was not taken over
+                    held = None
                 m.update_girsanov_sites(op[2])
             elif op[0] == "r":
                 m.relinearize()
             elif op[0] == "g":
                 m.update_girsanov_sites(op[1])
+            elif op[0] == "x":
+                tp = m._theta_p
+                m.plan.factor(tp.diag, tp.sub, tp.lin, aD=-2.0, aS=-1.0)
+            elif op[0] == "a":
+                m.data_nat1 = m.data_nat1 * 0.9
+                assert m._cq.site_lin is m.data_nat1
+            elif op[0] == "i":
+                m.data_nat1.mul_(1.1)
+                m._sites_moved()
+            if op[0] in "xai":
+                if m is b:
+                    assert b._ahead.rec is not None       # (the ELBO of the step before made one)
+                    held = b._ahead.consumed
+                continue                                  # (an ELBO here would make a record for the new state)
             out.append(host(m.classic_elbo_per_trajectory()))
     b.plan.check_info()
     assert used >= 6                    # records were made and consumed, not just dropped
+    assert b._ahead.consumed > used     # ... also after the invalidations
     np.testing.assert_allclose(np.array(got), np.array(want), rtol=1e-12)
     assert_close(host(b.plan.unpack(amd.VEC, b.full_sites().lin)), host(a.plan.unpack(amd.VEC, a.full_sites().lin)), rtol=1e-12)
 
@@ -1971,12 +1993,12 @@ def test_kalman_filter_sites_fused_output_dim_2(amd, tag, bs):
     kf = KalmanFilterWithSites(ssm, em, sites)
     np.testing.assert_allclose(float(kf.log_likelihood()), g["log_lik_total"], rtol=1e-7)
     # posterior marginals projected onto f
-    from vidp_amd.variational_cvi import GaussianProcessWithSitesBase, _predict_f_fused
+    from vidp_amd.variational_cvi import GaussianProcessWithSitesBase
     class _M:      # the attributes _predict_f_fused reads
         pass
     m = _M()
     m.dist_p, m.sites, m._emission = ssm, sites, (lambda: em)
-    Fmu, Fvar = _predict_f_fused(m)
+    Fmu, Fvar = GaussianProcessWithSitesBase._predict_f_fused(m)
     sm, sc = g["smooth_means"], np.broadcast_to(g["smooth_covs"], bs + g["smooth_covs"].shape)
     assert_close(host(Fmu), np.einsum("ai,...ti->...ta", g["H"], sm))
     assert_close(host(Fvar), np.einsum("ai,...tij,aj->...ta", g["H"], sc, g["H"]))

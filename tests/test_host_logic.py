@@ -255,3 +255,81 @@ def test_general_inverse():
         np.testing.assert_allclose((X @ M).numpy(), np.broadcast_to(np.eye(d), (5, d, d)), atol=1e-11)
         np.testing.assert_allclose(X.numpy(), np.linalg.inv(M.numpy()), rtol=1e-9, atol=1e-11)
 
+
+
+def test_stamp_matches_only_the_same_tensors_at_the_same_version():
+    """stamps.Stamp: a key over tensors (object + version, held weakly) and plain values; stamps.wrote: a write torch did not see."""
+    import gc
+    from vidp_amd.stamps import Stamp, wrote
+    t = torch.zeros(3, dtype=torch.float64)
+    u = torch.ones(3, dtype=torch.float64)
+    s = Stamp(t, u, 0.5, (4, 2))
+    assert s.matches(t, u, 0.5, (4, 2))
+    assert not s.matches(t, u, 0.5) and not s.matches(t, u, 0.5, (4, 2), None)      # another number of parts
+    assert not s.matches(t, u, 0.3, (4, 2)) and not s.matches(t, u, 0.5, (4, 3))    # another value
+    assert not s.matches(u, t, 0.5, (4, 2)) and not s.matches(t, 0.5, u, (4, 2))    # other tensors / a value where a tensor was
+    assert not s.matches(t.view(3), u, 0.5, (4, 2))                                 # a view of the same storage is another object
+    wrote(u, None)
+    assert not s.matches(t, u, 0.5, (4, 2)) and Stamp(t, u).matches(t, u)           # written behind torch's back
+    s = Stamp(t)
+    t.add_(1.0)
+    assert not s.matches(t)                                                         # in-place edit through torch
+    s = Stamp(t)
+    del t
+    gc.collect()
+    t = torch.zeros(3, dtype=torch.float64)                                         # same shape and dtype, possibly the same address
+    assert not s.matches(t)                                                         # the stamped tensor is gone: never a match
+
+
+def test_record_ahead_bookkeeping():
+    """variational_cvi_sde._Ahead (the record CVISitesSDE's cross-step pipelining makes ahead) driven without a GPU: CPU site tensors
+    [4, 2] and [3], stand-ins for the plan (an epoch) and the structured state (site_sym, version)."""
+    from types import SimpleNamespace
+    from vidp_amd.stamps import wrote
+    from vidp_amd.variational_cvi_sde import _Ahead
+    plan = SimpleNamespace(epoch=0)
+    cq = SimpleNamespace(site_sym=torch.full((3,), 2.0, dtype=torch.float64), version=0)
+    site = SimpleNamespace(lin=torch.ones((4, 2), dtype=torch.float64))
+    calls = []
+
+    def launch(lin, sym, lr):       # the blend towards a zero gradient, then "the factorisation"
+        lin.copy_((1 - lr) * site.lin)
+        sym.copy_((1 - lr) * cq.site_sym)
+        plan.epoch += 1
+        calls.append(lr)
+        return "factor"
+
+    def update(ahead, lr):          # what update_data_sites does with the answer
+        got = ahead.accept(lr, site.lin, cq, plan)
+        if got is not None:
+            site.lin, cq.site_sym = got
+        return got
+
+    ahead = _Ahead()
+    ahead.drop()                                                   # nothing to drop
+    assert ahead.rec is None and not ahead.take(site.lin, cq, plan)
+    assert update(ahead, 0.5) is None and ahead.lr == 0.5          # no record yet; the learning rate is remembered
+    # another learning rate: refused and dropped
+    assert ahead.make(site.lin, cq, plan, launch) == "factor" and calls == [0.5] and ahead.rec is not None
+    assert update(ahead, 0.3) is None and ahead.rec is None and ahead.consumed == 0
+    # the same learning rate: the buffers are exchanged, the record is taken exactly once
+    assert update(ahead, 0.5) is None
+    ahead.make(site.lin, cq, plan, launch)
+    old, spare = (site.lin, cq.site_sym), tuple(ahead.bufs)
+    assert update(ahead, 0.5) is not None and ahead.consumed == 1
+    assert site.lin is spare[0] and cq.site_sym is spare[1] and ahead.bufs[0] is old[0] and ahead.bufs[1] is old[1]
+    np.testing.assert_array_equal(site.lin.numpy(), np.full((4, 2), 0.5))
+    assert ahead.take(site.lin, cq, plan) and not ahead.take(site.lin, cq, plan) and ahead.rec is None
+    # another factorisation on the plan between accept and take
+    ahead.make(site.lin, cq, plan, launch)
+    assert update(ahead, 0.5) is not None and ahead.consumed == 2
+    plan.epoch += 1
+    assert not ahead.take(site.lin, cq, plan) and ahead.rec is None
+    # a site tensor written after the record was made
+    ahead.make(site.lin, cq, plan, launch)
+    wrote(cq.site_sym)
+    assert update(ahead, 0.5) is None and ahead.rec is None and ahead.consumed == 2
+    # a Girsanov update (the state's version) after the record was made
+    ahead.make(site.lin, cq, plan, launch)
+    cq.version += 1
+    assert update(ahead, 0.5) is None and ahead.rec is None and ahead.consumed == 2

@@ -86,7 +86,7 @@ def load_cvi_model(path, model):
     model.data_nat1, model.data_nat2 = dev(n1.reshape(B * n, d)), dev(n2.reshape(B * n, d, d))
     g = PackedBTDNat(pl.pack(VEC, dev(g1)), pl.pack(SYM, dev(gd)), pl.pack(FULL, dev(gs)))
     model._rebuild_theta_q(g)
-    model._started, model._q = True, None
+    model._sites_moved()
     return model
 
 

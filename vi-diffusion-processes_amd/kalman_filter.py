@@ -5,13 +5,16 @@ kalman_filter.py:32-639).  Posterior precision = prior block-tri-diagonal precis
 precision; one block Cholesky (HIP forward sweep) gives the log-determinant and |L^{-1} G^T Sigma^{-1} y|^2.
 The per-observation algebra (output_dim 1-2) is tiny batched torch work; everything sequential in T runs in the sweeps.
 """
+import ctypes
 import math
 import os
 
 import torch
 
-from . import linalg
+from . import _lib, linalg
 from ._lib import FULL, SYM, TRI, VEC
+from .packed import _ptr, _stream
+from .stamps import Stamp
 from .state_space_model import StateSpaceModel
 
 
@@ -168,8 +171,6 @@ class KalmanFilter(BaseKalmanFilter):
 def fused_sites_call(ssm, emission, sites):
     """(KfSites struct, keep-alive tuple) for the fused Kalman-filter-with-sites entry points (mfgm_kf_sites_*), or None when the
     problem does not qualify: state_dim <= 8, output_dim <= 2, a time-invariant emission matrix, one site per time point."""
-    import ctypes
-    from . import _lib
     Hc = getattr(emission, "constant_matrix", None)
     if Hc is None or ssm.d > 8 or ssm.plan.d != ssm.d or Hc.shape[0] > 2 or os.environ.get("VIDP_FUSED_KF", "1") == "0":
         return None
@@ -200,6 +201,13 @@ def fused_sites_call(ssm, emission, sites):
     return sv, (n1c, n2c, hmu), cache
 
 
+def factored_for(cache, keep, pl):
+    """Record that the factorisation now in the scratch (L, y) and the plan's workspace is that of the system of these sites.  With a
+    zero-mean prior the prediction at the data solves the same system with the same right-hand side, and reuses it while the stamp
+    (site tensors, plan epoch) matches; None otherwise."""
+    cache["factor_of"] = Stamp(keep[0], keep[1], pl.epoch) if cache["zero_mean"] else None
+
+
 def _kf_scratch(cache, pl, names):
     bufs = cache.setdefault("bufs", {})
     kinds = dict(D=SYM, r=VEC, L=TRI, y=VEC, Sig=SYM, x=VEC)
@@ -221,9 +229,6 @@ class KalmanFilterWithSites(BaseKalmanFilter):
     def log_likelihood(self):
         """kalman_filter.py:184-255.  With a time-invariant emission matrix: one library call (assembly of the posterior precision
         in the packed layout, the forward sweeps, the observation-term sums), a handful of [B]-sized operations here."""
-        import ctypes
-        from .packed import _ptr, _stream
-        from . import _lib
         ssm, pl = self.prior_ssm, self.prior_ssm.plan
         call = fused_sites_call(ssm, self.emission, self.sites)
         if call is None:
@@ -240,10 +245,7 @@ class KalmanFilterWithSites(BaseKalmanFilter):
         _lib.check(pl.lib.mfgm_kf_sites_elbo(pl.h, ctypes.byref(sv), _ptr(pr["diag"]), _ptr(pr["sub"]), _ptr(b["D"]), _ptr(b["r"]),
                                              _ptr(b["L"]), _ptr(b["y"]), _ptr(pr["sumlogchol"]), cst, None, None, _ptr(total), _ptr(pl.ws),
                                              _ptr(pl.info), _stream()), "mfgm_kf_sites_elbo")
-        # the factorisation now in (L, y) and the workspace belongs to these sites: with a zero-mean prior the prediction at the data
-        # solves the same system with the same right-hand side (_predict_f_fused reuses it).  The site tensors are kept alive here,
-        # so that `is` identifies them.
-        cache["factor_of"] = (keep[0], keep[0]._version, keep[1], keep[1]._version, pl.epoch) if cache["zero_mean"] else None
+        factored_for(cache, keep, pl)      # (GaussianProcessWithSitesBase._predict_f_fused reuses it)
         if os.environ.get("VIDP_EAGER_CHECK", "0") == "1":
             pl.check_info()
         return total[0]

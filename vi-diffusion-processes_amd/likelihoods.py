@@ -12,11 +12,12 @@ LinearReadout, last, lets the diffusion models see their state through f = H x +
 (DESIGN.md section 19).
 """
 import math
-import weakref
 
 import torch
 
-from . import linalg
+from . import _lib, linalg
+from .packed import _ptr, _stream
+from .stamps import Stamp
 
 
 class MultivariateGaussian:
@@ -70,14 +71,12 @@ class MultivariateGaussian:
         """
         # both gradients depend on the observations only: computed once per observation TENSOR OBJECT and version (a raw address
         # is no key: the caching allocator hands freed blocks back at the same address with the same shape)
-        c = self._g_cache
-        if (c is None or c[0]() is not observations or c[1] != observations._version or c[2] != tuple(f_covariances.shape)
-                or c[3] != self.inv_covariance._version):
-            Sinv = self.inv_covariance
+        c, Sinv = self._g_cache, self.inv_covariance
+        if c is None or not c[0].matches(observations, tuple(f_covariances.shape), Sinv):
             g1 = (Sinv * observations[..., None, :]).sum(-1)           # S^{-1} y (S symmetric)
             g2 = (-0.5 * Sinv).expand(f_covariances.shape).contiguous()
-            c = self._g_cache = (weakref.ref(observations), observations._version, tuple(f_covariances.shape), Sinv._version, g1, g2)
-        return c[4], c[5]
+            c = self._g_cache = (Stamp(observations, tuple(f_covariances.shape), Sinv), g1, g2)
+        return c[1], c[2]
 
 
 class Gaussian:
@@ -110,10 +109,9 @@ class Gaussian:
         # (y / v, -1/2 / v) depend on the observations only: computed once per observation tensor object and version
         v = self.variance
         c = getattr(self, "_g_cache", None)
-        if c is None or c[0]() is not observations or c[1] != observations._version or c[2] != tuple(f_vars.shape) or c[3] != v:
-            c = self._g_cache = (weakref.ref(observations), observations._version, tuple(f_vars.shape), v, observations / v,
-                                 torch.full_like(f_vars, -0.5 / v))
-        return c[4], c[5]
+        if c is None or not c[0].matches(observations, tuple(f_vars.shape), v):
+            c = self._g_cache = (Stamp(observations, tuple(f_vars.shape), v), observations / v, torch.full_like(f_vars, -0.5 / v))
+        return c[1], c[2]
 
 
 # ---- scalar non-Gaussian likelihoods (gpflow.likelihoods.Bernoulli / Poisson, the ones the reference's CVI walkthroughs fit) ----------
@@ -172,8 +170,6 @@ class ScalarQuadratureLikelihood:
         return all(t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.shape == f_means.shape for t in ts)
 
     def _launch(self, f_means, f_vars, observations, ve=False, grads=False):
-        from . import _lib
-        from .packed import _ptr, _stream
         n = f_means.numel()
         mk = lambda: torch.empty(f_means.shape, dtype=torch.float64, device=f_means.device)
         out_ve = mk() if ve else None
@@ -344,8 +340,6 @@ class PEPScalarLikelihood:
         return all(t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.shape == Fmu.shape for t in ts)
 
     def _launch(self, Fmu, Fvar, Y, alpha, want_grads):
-        from . import _lib
-        from .packed import _ptr, _stream
         mk = lambda: torch.empty(Fmu.shape, dtype=torch.float64, device=Fmu.device)
         lz = mk()
         d1, d2 = (mk(), mk()) if want_grads else (None, None)
@@ -466,7 +460,6 @@ class LinearReadout:
     def descriptor(self):
         """_lib.Readout of the emission, the offset and the factors' current parameters (native kinds only); rebuilt when a parameter
         has changed."""
-        from . import _lib
         if not self.native_kinds:
             raise TypeError("a LinearReadout with a factor other than Gaussian, Bernoulli or Poisson (or d > 8) has no native description")
         key = tuple((type(b), b.variance if type(b) is Gaussian else b.param) for b in self.likelihoods)

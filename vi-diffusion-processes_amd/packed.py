@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import FULL, SYM, TRI, VEC
+from .stamps import wrote
 
 
 def _ptr(t):
@@ -102,7 +103,7 @@ class Plan:
         out = self.zeros(kind) if out is None else out
         _lib.check(self.lib.mfgm_pack(self.h, kind, _ptr(natural), n_nodes, _ptr(out), _stream()), "mfgm_pack")
         if given:
-            torch.autograd.graph.increment_version(out)      # written behind torch's back: caches keyed on ._version must notice
+            wrote(out)
         return out
 
     def unpack(self, kind, packed, n_nodes=None):
@@ -273,8 +274,7 @@ class Plan:
         _lib.check(self.lib.mfgm_readout_site_update(self.h, ctypes.byref(readout), _ptr(mu), _ptr(Sig), int(bool(gathered)),
                                                      _ptr(node_ids), n, _ptr(y), _ptr(theta_lin), _ptr(theta_diag), _ptr(sites_vec),
                                                      _ptr(sites_sym), float(lr), _stream()), "mfgm_readout_site_update")
-        for t in (theta_lin, theta_diag, sites_vec, sites_sym):
-            torch.autograd.graph.increment_version(t)      # written behind torch's back
+        wrote(theta_lin, theta_diag, sites_vec, sites_sym)
 
     def readout_obs_ve(self, readout, mu, Sig, node_ids, n_per, y, out_mu=None, out_cov=None, partials=False):
         """Per-trajectory variational expectations under a linear-readout likelihood at the observation nodes, gathered from the packed

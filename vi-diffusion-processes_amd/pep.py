@@ -14,7 +14,9 @@ import math
 import numpy as np
 import torch
 
-from . import linalg
+from . import _lib, linalg
+from .packed import _ptr, _stream
+from .stamps import wrote
 from .variational_cvi import GaussianProcessWithSitesBase, back_project_nats
 
 
@@ -128,8 +130,6 @@ class PowerExpectationPropagation(GaussianProcessWithSitesBase):
                 and all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() for t in ts) and fmu.numel() == self.num_data)
 
     def _launch(self, fmu, fvar, lr, idx, k, lnorm, e_out, skipped):
-        from . import _lib
-        from .packed import _ptr, _stream
         lik, s = self._likelihood, self.sites
         _lib.check(_lib.load().mfgm_pep_sites(lik.kind, self.num_data, _ptr(fmu), _ptr(fvar), _ptr(self._observations), float(lik.param),
                                               self.alpha, float(lr), _ptr(idx), k, _ptr(s.nat1), _ptr(s.nat2), _ptr(lnorm), _ptr(e_out),
@@ -157,8 +157,7 @@ class PowerExpectationPropagation(GaussianProcessWithSitesBase):
         s = self.sites
         if self._native(fmu, fvar):
             self._launch(fmu, fvar, self.learning_rate, idx, k, s.log_norm, None, self.skipped)
-            for t in (s.nat1, s.nat2, s.log_norm):
-                torch.autograd.graph.increment_version(t)     # written behind torch's back: the factor caches key on ._version
+            wrote(s.nat1, s.nat2, s.log_norm)
             return
         # torch route (a likelihood without a kind): the same update, element-wise
         a, lr = self.alpha, self.learning_rate
@@ -183,10 +182,6 @@ class PowerExpectationPropagation(GaussianProcessWithSitesBase):
         """Host count of skipped site updates so far (synchronises)."""
         return int(self.skipped.item())
 
-    def elbo(self):
-        """Log marginal likelihood of the model whose likelihood terms are the Gaussian sites (pep.py:217-221)."""
-        return self.log_likelihood()
-
     def _dist_p_normalizer(self):
         if self._norm_p is None:                     # the prior is fixed
             self._norm_p = self.dist_p.normalizer()
@@ -205,35 +200,9 @@ class PowerExpectationPropagation(GaussianProcessWithSitesBase):
         scalar.  At the fixed point of a Gaussian likelihood it is the exact log marginal likelihood for every alpha."""
         return self._dist_q_normalizer() - self._dist_p_normalizer() + self.compute_log_norm().sum() / self.alpha
 
-    def step_graph(self):
-        """`update_sites(); elbo()` over all sites captured once in a HIP graph, as CVIGaussianProcess.step_graph: returns a callable that
-        replays it and hands back the ELBO (a device scalar that every replay overwrites)."""
-        from .kalman_filter import fused_sites_call
-        self.predict_f_at_data()
-        self.elbo()
-        call = fused_sites_call(self.dist_p, self._emission(), self.sites)
-        cache = call[2] if call is not None else {}
-        cache["factor_of"] = None                   # capture factor + selected inverse + projection, not the shortcut
-        pl = self.dist_p.plan
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self.update_sites()
-            e = self.elbo()
-        cache["factor_of"] = None
+    def kernel_changed(self):
+        super().kernel_changed()
+        self._norm_p = None
 
-        def step():
-            graph.replay()
-            for t in (self.sites.nat1, self.sites.nat2, self.sites.log_norm):
-                torch.autograd.graph.increment_version(t)
-            pl.epoch += 1
-            cache["factor_of"] = None
-            return e
-        step.graph = graph
-        return step
-
-    def predict_log_density(self, input_data, full_output_cov=False):
-        """log p(y* | data) per point (pep.py:232-247): the likelihood's predict_log_density of posterior.predict_f."""
-        X, Y = input_data
-        f_mean, f_var = self.posterior.predict_f(X, full_output_cov=full_output_cov)
-        return self._likelihood.predict_log_density(f_mean, f_var, Y)
+    def _step_sites(self):
+        return self.sites.nat1, self.sites.nat2, self.sites.log_norm

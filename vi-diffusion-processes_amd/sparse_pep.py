@@ -21,13 +21,17 @@ Gaussian keep their sites and are counted in `skipped`.
 With several points per interval the points share one tied site (the reference's `fraction_sites`), so the fixed point under a
 non-Gaussian likelihood is that of tied-site Power EP.
 """
+import ctypes
 import math
 
 import torch
 
+from . import _lib
 from .conditionals import _conditional_statistics, base_conditional_predict
+from .packed import _ptr, _stream
 from .pep import gradient_correction
 from .sparse_variational_cvi import SparseCVIGaussianProcess
+from .stamps import wrote
 
 
 def _cond_stats(time_points, inducing_points, kernel):
@@ -208,9 +212,7 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
         """The posterior over the inducing states for the given sites, as a StateSpaceModel (sparse_pep.py:197-231)."""
         if not self._on_device():
             raise NotImplementedError("the posterior state-space model needs the sites on the device")
-        from . import _lib
         from ._lib import FULL, SYM, VEC
-        from .packed import _ptr, _stream
         from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
         p = self.dist_p
         pl, T, d = p.plan, p.T, p.d
@@ -289,9 +291,6 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
                 and self.skipped.is_cuda)
 
     def _launch(self, data, observations, lr, lnorm, e_out, skipped):
-        import ctypes
-        from . import _lib
-        from .packed import _ptr, _stream
         m = self._marginals()
         self._sync_sites()
         lik = self._pep
@@ -335,10 +334,8 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
         data = self._data(input_data) if self._on_device() else None
         if self._native(data):
             self._launch(data, input_data[1], self.learning_rate, self.log_norm, None, self.skipped)
-            if self._packed:
-                self._nat2 = None            # a dense copy handed out earlier is stale now
-            torch.autograd.graph.increment_version(self.log_norm)
-            self._version += 1
+            wrote(self.log_norm)
+            self._sites_written()
             return
         n1, n2, ln, _, sk = self._torch_update(input_data, self.learning_rate)
         self.nat1, self.nat2 = n1, n2

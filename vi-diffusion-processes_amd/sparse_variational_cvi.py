@@ -4,14 +4,18 @@ Host-side mirror of markovflow/models/sparse_variational_cvi.py `SparseCVIGaussi
 [M+1, 2d, 2d] sites into the block-tri-diagonal natural parameters and the data -> site segment sums (a Python list of
 M+1 reduce_sums in the reference, :199-213) are single index_add operations; the posterior refresh runs in the HIP sweeps.
 """
+import ctypes
 import os
 
 import torch
 
+from . import _lib
 from ._lib import FULL, SYM, VEC
 from .conditionals import _conditional_statistics, conditional_statistics
+from .packed import Plan, _ptr, _stream
 from .posterior import ConditionalProcess
 from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
+from .stamps import Stamp
 from .variational_cvi import back_project_nats
 
 
@@ -47,7 +51,6 @@ class SparseCVIGaussianProcess:
         self._shard = None
         if shard is not None:
             from .distributed import ChainShard
-            from .packed import Plan
             if sd <= 8 or inducing_points.dim() != 1:
                 raise ValueError("a chain is shared between processes on the wide path only (state dimension > 8, one chain)")
             if not isinstance(shard, dict):
@@ -85,7 +88,7 @@ class SparseCVIGaussianProcess:
 
     def _sync_sites(self):
         """Packed mode: take back a dense `nat2` that was edited in place since it was handed out."""
-        if self._packed and self._nat2 is not None and self._nat2._version != self._nat2_seen:
+        if self._packed and self._nat2 is not None and not self._nat2_seen.matches(self._nat2):
             self.nat2 = self._nat2
 
     @property
@@ -98,7 +101,7 @@ class SparseCVIGaussianProcess:
                 flat[:, self._pack_index()] = self._nat2q
                 low = flat.view(-1, d2, d2)
                 self._nat2 = low + low.transpose(-1, -2) - torch.diag_embed(torch.diagonal(low, dim1=-2, dim2=-1))
-                self._nat2_seen = self._nat2._version
+                self._nat2_seen = Stamp(self._nat2)
         return self._nat2
 
     @nat2.setter
@@ -106,13 +109,25 @@ class SparseCVIGaussianProcess:
         self._nat2 = value
         self._version += 1
         if self._packed:
-            self._nat2_seen = value._version
+            self._nat2_seen = Stamp(value)
             self._nat2q = value.reshape(value.shape[0], -1)[:, self._pack_index()].contiguous()
 
-    def _key(self):
+    def _sites_written(self):
+        """A library call wrote the resident sites: a dense `nat2` handed out earlier is stale, and every stamp on the sites moves."""
+        if self._packed:
+            self._nat2 = None
+        self._version += 1
+
+    def _site_parts(self):
         self._sync_sites()
-        n2 = self._nat2q if self._packed else self._nat2
-        return (self._version, id(self._nat1), self._nat1._version, id(n2), n2._version)
+        return self._version, self._nat1, self._nat2q if self._packed else self._nat2
+
+    def _key(self):
+        """Stamp of the current sites: what every cached posterior quantity is kept for."""
+        return Stamp(*self._site_parts())
+
+    def _current(self, stamp):
+        return stamp.matches(*self._site_parts())
 
     @property
     def kernel(self):
@@ -152,13 +167,10 @@ class SparseCVIGaussianProcess:
         """Per-data-set constants of the fused route: CSR offsets of the data points per inter-inducing interval, w_i = H P_i, c_i = H T_i H^T
         (conditionals.py:207-256: functions of the time points and the kernel only), the kernel's initial state; or None when the
         route does not apply (unsorted or batched time points)."""
-        import ctypes
-        import weakref
-        from . import _lib
         time_points, observations = input_data
         c = getattr(self, "_data_cache", None)
-        if c is not None and c["ref"]() is time_points and c["ver"] == time_points._version:
-            return c["val"]
+        if c is not None and c[0].matches(time_points):
+            return c[1]
         val = None
         z = self.inducing_inputs
         if (time_points.dim() == 1 and z.dim() == 1 and time_points.is_cuda and os.environ.get("VIDP_FUSED_SPARSE", "1") != "0"
@@ -191,7 +203,7 @@ class SparseCVIGaussianProcess:
             val = dict(struct=sd, keep=(seg, w, cc, pm, pc), N=N, own=own)
         if val is None and self._shard is not None:
             raise ValueError("a shared chain needs sorted, un-batched time points on the device")
-        self._data_cache = dict(ref=weakref.ref(input_data[0]), ver=input_data[0]._version, val=val)
+        self._data_cache = (Stamp(input_data[0]), val)
         return val
 
     def _prior_natural(self):
@@ -249,14 +261,11 @@ class SparseCVIGaussianProcess:
         return float((ev.max(-1).values / ev.min(-1).values.clamp_min(1e-300)).max())
 
     def _fused_theta(self):
-        import os
         return (self._inverse_form() and os.environ.get("VIDP_FUSED_THETA", "1") != "0" and self.nat1.is_contiguous()
                 and (self._packed or self.nat2.is_contiguous()))
 
     def _theta(self):
         """Posterior naturals of the current sites, packed (lin, diag, sub): one pass over the sites (mfgm_sparse_theta)."""
-        from . import _lib
-        from .packed import _ptr, _stream
         p = self.dist_p
         pl, T, d = p.plan, p.T, p.d
         pn = self._prior_natural()
@@ -276,7 +285,7 @@ class SparseCVIGaussianProcess:
         """Posterior marginals of the inducing states for the current sites: one factorisation + selected inverse, cached until the
         sites move.  dict(mu [T, d], Sig [T, d, d], Sub [T, d, d] natural; packed Sig / Sub / x; log|L|)."""
         m = getattr(self, "_marg", None)
-        if m is not None and m["version"] == self._key():
+        if m is not None and self._current(m["version"]):
             return m
         p = self.dist_p
         pl, T, d = p.plan, p.T, p.d
@@ -314,23 +323,19 @@ class SparseCVIGaussianProcess:
     def _own_observations(data, observations):
         """observations[data["own"]] as ONE tensor object per (data set, observation tensor, version)."""
         c = data.get("y_own")
-        if c is None or c[0] is not observations or c[1] != observations._version:
-            c = data["y_own"] = (observations, observations._version, observations[data["own"]])
-        return c[2]
+        if c is None or not c[0].matches(observations):
+            c = data["y_own"] = (Stamp(observations), observations[data["own"]])
+        return c[1]
 
     def _predict_f_data(self, data):
         """(fmu, fvar) [N, 1] at the data points from the cached marginals (mfgm_sparse_predict)."""
-        import ctypes
-        from . import _lib
-        from .packed import _ptr, _stream
         c = getattr(self, "_pred_cache", None)
-        if c is not None and c[0] == self._key() and c[1] is data:
+        if c is not None and self._current(c[0]) and c[1] is data:
             return c[2]          # the sites have not moved since these were computed (the ELBO of the previous iteration)
         m = self._marginals()
         pl = self.dist_p.plan if self._shard is None else self._shard.plan
         N = data["N"]
         out = torch.empty((2, max(N, 1)), dtype=torch.float64, device=pl.device)[:, :N]
-        import os
         if pl.wide and (self._shard is not None or os.environ.get("VIDP_FUSED_SPARSE_KL", "1") != "0"):
             # the pass over the pair covariances also takes the trace / Mahalanobis terms of KL[q || p] (what classic_elbo asks for next)
             pn = self._prior_natural()
@@ -352,9 +357,6 @@ class SparseCVIGaussianProcess:
         data = self._data(input_data)
         if data is None:
             return self._update_sites_generic(input_data)
-        import ctypes
-        from . import _lib
-        from .packed import _ptr, _stream
         time_points, observations = input_data
         fx_mus, fx_covs = self._predict_f_data(data)
         # the gradients alone: the reference's local_objective_and_gradients also returns the objective value, which update_sites drops
@@ -367,11 +369,10 @@ class SparseCVIGaussianProcess:
         if self._packed:
             _lib.check(pl.lib.mfgm_sparse_site_update_q(ctypes.byref(data["struct"]), _ptr(g1), _ptr(g2), float(self.learning_rate),
                                                         _ptr(self._nat1), _ptr(self._nat2q), _stream()), "mfgm_sparse_site_update_q")
-            self._nat2 = None            # a dense copy handed out earlier is stale now
         else:
             _lib.check(pl.lib.mfgm_sparse_site_update(ctypes.byref(data["struct"]), _ptr(g1), _ptr(g2), float(self.learning_rate),
                                                       _ptr(self._nat1), _ptr(self._nat2), _stream()), "mfgm_sparse_site_update")
-        self._version += 1
+        self._sites_written()
         if self._shard is not None:
             self._pass_edge_site()
 
@@ -387,9 +388,7 @@ class SparseCVIGaussianProcess:
             d2 = self._nat1.shape[-1]
             self._nat1[hi].copy_(every[sh.rank + 1, :d2])
             n2[hi].copy_(every[sh.rank + 1, d2:].view(n2[hi].shape))
-            if self._packed:
-                self._nat2 = None
-            self._version += 1
+            self._sites_written()
 
     def _gather_sites(self):
         """A shared chain: the sites of every process on every process (dist_q / posterior of the whole chain; not on the training path)."""
@@ -399,9 +398,7 @@ class SparseCVIGaussianProcess:
             own = torch.zeros_like(t)
             own[self._m_lo:self._m_hi] = t[self._m_lo:self._m_hi]
             t.copy_(sh.allreduce(own))
-        if self._packed:
-            self._nat2 = None
-        self._version += 1
+        self._sites_written()
 
     def _update_sites_generic(self, input_data):
         time_points, observations = input_data
@@ -414,9 +411,8 @@ class SparseCVIGaussianProcess:
         s1 = torch.zeros_like(self.nat1).index_add_(0, idx, theta_linear)
         s2 = torch.zeros_like(self.nat2).index_add_(0, idx, lik_nat2)
         lr = self.learning_rate
-        self.nat1 = (1 - lr) * self.nat1 + lr * s1
+        self.nat1 = (1 - lr) * self.nat1 + lr * s1      # (the setters move the stamps)
         self.nat2 = (1 - lr) * self.nat2 + lr * s2
-        self._version += 1
 
     def classic_elbo(self, input_data):
         """sum_i E_q log p(y_i | f_i) - KL[q(s_Z) || p(s_Z)] (sparse_variational_cvi.py:270-292)."""
@@ -431,12 +427,9 @@ class SparseCVIGaussianProcess:
         y_own = self._own_observations(data, observations)
         ve_terms = getattr(self._likelihood, "variational_expectations_terms", None)
         kc = getattr(self, "_kl_cache", None)
-        if ve_terms is not None and self._shard is None and kc is not None and kc[0] == self._key():
+        if ve_terms is not None and self._shard is None and kc is not None and self._current(kc[0]):
             # every piece of the bound is a device scalar by now: assemble  VE - KL  in one launch (a dozen scalar torch kernels otherwise),
             # NaN-poisoned when a pivot block of the factorisation was not positive definite
-            import ctypes
-            from . import _lib
-            from .packed import _ptr, _stream
             m, pn, p = self._marginals(), self._prior_natural(), self.dist_p
             c, w, (t1, t2) = ve_terms(fx_mus, fx_covs, y_own)
             terms = torch.cat([t1, t2, kc[1].reshape(1), kc[2].reshape(1), pn["nat"]["sumlogchol"].reshape(1), m["logdetL"].reshape(1)])
@@ -459,7 +452,7 @@ class SparseCVIGaussianProcess:
             tot = self._shard.allreduce(torch.cat([ve.reshape(1), kc[1], kc[2], m["logdetL"].reshape(1)]))
             kl = 0.5 * (tot[1] + tot[2] - float(p.T * p.d) + 2.0 * pn["nat"]["sumlogchol"].sum() + 2.0 * tot[3])
             return tot[0] - kl
-        if kc is not None and kc[0] == self._key():
+        if kc is not None and self._current(kc[0]):
             tr, mh = kc[1], kc[2]          # taken together with the predictions (mfgm_sparse_predict_kl)
         else:
             tr, mh = pl.kl_terms(s["Sig"], s["Sub"], s["x"], pn["nat"]["diag"], pn["nat"]["sub"], self._prior_mean_packed(), aD=-2.0, aS=-1.0)

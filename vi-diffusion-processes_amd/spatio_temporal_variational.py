@@ -17,13 +17,15 @@ mfgm_sparse_site_update_q instead, the yardstick of tools/st_rate.py).
 """
 import ctypes
 import os
-import weakref
 
 import torch
 
-from .kernels import SparseSpatioTemporalKernel
+from . import _lib
+from .kernels import PiecewiseKernel, SparseSpatioTemporalKernel
+from .packed import _ptr, _stream
 from .sparse_pep import _cond_stats
 from .sparse_variational_cvi import SparseCVIGaussianProcess
+from .stamps import Stamp
 
 MAX_STATE_DIM = 32
 
@@ -45,7 +47,6 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
             raise NotImplementedError("one chain: inducing_time [M_t] and inducing_space [Ms, p]; batched inducing points are not supported")
         if mean_function is not None and not callable(mean_function):
             raise ValueError("mean_function must be a callable X -> [N, 1]")
-        from .kernels import PiecewiseKernel
         if isinstance(kernel_time, PiecewiseKernel):
             raise NotImplementedError("SpatioTemporalSparseCVI does not take a PiecewiseKernel as its time kernel: the stacked state is a "
                                       "Sum of stationary kernels")
@@ -110,15 +111,14 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
         None where the torch route applies."""
         X, _ = input_data
         c = getattr(self, "_data_cache", None)
-        if c is not None and c["ref"]() is X and c["ver"] == X._version:
-            return c["val"]
+        if c is not None and c[0].matches(X):
+            return c[1]
         val = self._build_data(X)
-        self._data_cache = dict(ref=weakref.ref(X), ver=X._version, val=val)
+        self._data_cache = (Stamp(X), val)
         return val
 
     def _build_data(self, X):
         """The constants of _data for the inputs X, uncached."""
-        from . import _lib
         val = None
         z = self.inducing_inputs
         if (X.dim() == 2 and X.is_cuda and z.is_cuda and os.environ.get("VIDP_FUSED_SPARSE", "1") != "0"
@@ -154,7 +154,7 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
     def _predict_f_data(self, data):
         """(fmu, fvar) [N, 1] at the data points from the cached marginals, the mean function included."""
         c = getattr(self, "_pred_cache", None)
-        if c is not None and c[0] == self._key() and c[1] is data:
+        if c is not None and self._current(c[0]) and c[1] is data:
             return c[2]
         res = self._predict_compute(data)
         self._pred_cache = (self._key(), data, res)
@@ -164,8 +164,6 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
         if not data["factored"]:
             fmu, fvar = super()._predict_f_data(data)          # (it leaves a cache entry without the mean function: the callers overwrite it)
         else:
-            from . import _lib
-            from .packed import _ptr, _stream
             m = self._marginals()
             pl, pn, N = self.dist_p.plan, self._prior_natural(), data["N"]
             out = torch.empty((2, max(N, 1)), dtype=torch.float64, device=pl.device)[:, :N]
@@ -198,8 +196,6 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
         data = self._data(input_data)
         if data is None:
             return self._update_sites_torch(input_data)
-        from . import _lib
-        from .packed import _ptr, _stream
         _, Y = input_data
         fmu, fvar = self._predict_f_data(data)
         g1, g2 = self._gradients(fmu, fvar, Y, data["mean"])
@@ -214,11 +210,10 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
         elif self._packed:
             _lib.check(lib.mfgm_sparse_site_update_q(st, _ptr(g1), _ptr(g2), lr, _ptr(self._nat1), _ptr(self._nat2q), _stream()),
                        "mfgm_sparse_site_update_q")
-            self._nat2 = None
         else:
             _lib.check(lib.mfgm_sparse_site_update(st, _ptr(g1), _ptr(g2), lr, _ptr(self._nat1), _ptr(self._nat2), _stream()),
                        "mfgm_sparse_site_update")
-        self._version += 1
+        self._sites_written()
 
     # ---- torch route (the correctness anchor) ----------------------------------------------------------------------------------------------
     def _dense_prior(self):
@@ -292,8 +287,8 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
     def space_time_predict_f(self, inputs):
         """Marginal (mean, variance) [N, 1] of f at inputs [N, p + 1] (:149-183)."""
         c = getattr(self, "_data_cache", None)
-        if c is not None and c["ref"]() is inputs and c["ver"] == inputs._version:
-            data = c["val"]                                          # the training inputs: their constants and predictions are cached
+        if c is not None and c[0].matches(inputs):
+            data = c[1]                                          # the training inputs: their constants and predictions are cached
             if data is not None:
                 return self._predict_f_data(data)
         else:
@@ -313,9 +308,8 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
         s1 = torch.zeros_like(self.nat1).index_add_(0, idx, g1 * w)
         s2 = torch.zeros_like(self.nat2).index_add_(0, idx, g2[:, :, None] * w[:, :, None] * w[:, None, :])
         lr = self.learning_rate
-        self.nat1 = (1 - lr) * self.nat1 + lr * s1
+        self.nat1 = (1 - lr) * self.nat1 + lr * s1      # (the setters move the stamps)
         self.nat2 = (1 - lr) * self.nat2 + lr * s2
-        self._version += 1
 
     def _kl(self):
         """KL[q(s(Z_t)) || p(s(Z_t))]."""

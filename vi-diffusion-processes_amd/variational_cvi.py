@@ -5,11 +5,18 @@ Host-side mirror of markovflow/models/variational_cvi.py (`GaussianProcessWithSi
 CVI tests).  Sites live on f = H s (one scalar site per data point); the posterior is prior naturals + back-projected
 sites, refreshed by the HIP sweeps.
 """
+import ctypes
+
 import torch
 
+from . import _lib, hyper, tape
 from ._lib import FULL, SYM, VEC
-from .kalman_filter import GaussianSitesNat, KalmanFilter, KalmanFilterWithSites
+from .kalman_filter import GaussianSitesNat, KalmanFilter, KalmanFilterWithSites, _kf_scratch, factored_for, fused_sites_call
+from .likelihoods import MultivariateGaussian
+from .packed import _ptr, _stream
+from .posterior import AnalyticPosteriorProcess, ConditionalProcess
 from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
+from .stamps import wrote
 
 
 def back_project_nats(nat1, nat2, C):
@@ -43,8 +50,6 @@ class GaussianProcessRegression:
     def posterior(self):
         """gaussian_process_regression.py:136-150: the Kalman posterior as an AnalyticPosteriorProcess with a MultivariateGaussian of
         the observation noise."""
-        from .likelihoods import MultivariateGaussian
-        from .posterior import AnalyticPosteriorProcess
         return AnalyticPosteriorProcess(self.posterior_state_space_model, self._kernel, self._time_points,
                                         MultivariateGaussian(self._chol_obs_covariance), self._mean_function)
 
@@ -63,7 +68,6 @@ class GaussianProcessRegression:
         R matrices for the LEG kernel) and to the scalar observation noise sigma^2 = chol_obs_covariance^2 (None when that is zero).
         One factorisation, one selected inverse and one score pass (hyper.py); the chains of a batch share the
         hyper-parameters, so their scores are summed."""
-        from . import hyper
         hyper.precheck(self._kernel)        # before the prior is built: a refused kernel launches nothing
         kf = self._kalman
         ll, grads, moments, disp = hyper.kernel_score(self._kernel, kf, self._time_points)
@@ -99,6 +103,7 @@ class GaussianProcessWithSitesBase:
         # nat1 = 0, nat2 = -1e-10 (variational_cvi.py:99-103)
         self.sites = GaussianSitesNat(torch.zeros_like(y), torch.full(tuple(y.shape) + (1,), -1e-10, dtype=y.dtype, device=y.device))
         self._dist_p = None
+        self._em = None
         self._cache = None
 
     @property
@@ -125,7 +130,7 @@ class GaussianProcessWithSitesBase:
         return self._dist_p
 
     def _emission(self):
-        if getattr(self, "_em", None) is None:       # the time points are fixed: one emission model per model object
+        if self._em is None:       # the time points are fixed: one emission model per model object
             self._em = self._kernel.generate_emission_model(self._time_points)
         return self._em
 
@@ -154,8 +159,8 @@ class GaussianProcessWithSitesBase:
     @property
     def posterior(self):
         """variational_cvi.py:146-153: the posterior process on dist_q."""
-        from .posterior import ConditionalProcess
-        return ConditionalProcess(self.dist_q, self._kernel, self._time_points, getattr(self, "_mean_function", None))
+        # (no mean function: the constructor's `mean_function` is the reference's signature only, the sites models have never used it)
+        return ConditionalProcess(self.dist_q, self._kernel, self._time_points)
 
     @property
     def posterior_kalman(self):
@@ -164,15 +169,25 @@ class GaussianProcessWithSitesBase:
     def log_likelihood(self):
         return self.posterior_kalman.log_likelihood()
 
+    def elbo(self):
+        """The marginal likelihood of the model whose likelihood terms are the Gaussian sites (variational_cvi.py:370-379, pep.py:217-221)."""
+        return self.log_likelihood()
+
     def loss(self):
         return -self.log_likelihood()
+
+    def predict_log_density(self, input_data, full_output_cov=False):
+        """log p(y* | data) per point (variational_cvi.py:406-421, pep.py:232-247): the likelihood's predict_log_density of
+        posterior.predict_f."""
+        X, Y = input_data
+        f_mean, f_var = self.posterior.predict_f(X, full_output_cov=full_output_cov)
+        return self._likelihood.predict_log_density(f_mean, f_var, Y)
 
     def log_likelihood_and_grad(self):
         """(ll, kernel_grads): the marginal likelihood of the model whose likelihood terms are the current Gaussian sites (what
         CVIGaussianProcess.elbo() returns, here through the unfused factorisation) and its gradient with respect to the kernel's
         hyper-parameters at FIXED sites, in the structure of kernel.hyperparameter_leaves() (CPU fp64 tensors): one factorisation,
         one selected inverse and one score pass (hyper.py)."""
-        from . import hyper
         hyper.precheck(self._kernel)        # before the prior is built: a refused kernel launches nothing
         ll, grads, _, _ = hyper.kernel_score(self._kernel, self.posterior_kalman, self._time_points)
         return ll, grads
@@ -183,8 +198,6 @@ class GaussianProcessWithSitesBase:
         self._dist_p = None
         self._em = None
         self._cache = None
-        if getattr(self, "_norm_p", None) is not None:      # PowerExpectationPropagation's cached prior normaliser
-            self._norm_p = None
 
     def predict_f_at_data(self):
         """posterior.predict_f(self.time_points): at the conditioning points this is (H mu, H Sigma H^T) of dist_q."""
@@ -201,45 +214,75 @@ class GaussianProcessWithSitesBase:
         em = self._emission()
         return em.project_state_to_f(mu), em.project_state_covariance_to_f(cov, full_output_cov=False)
 
+    def _predict_f_fused(self):
+        """predict_f at the data points through mfgm_kf_sites_predict (time-invariant emission, state_dim <= 8): assembly, sweeps and the
+        projection onto f in one library call; None when the model does not qualify."""
+        ssm = self.dist_p
+        call = fused_sites_call(ssm, self._emission(), self.sites)
+        if call is None:
+            return None
+        sv, keep, cache = call
+        pl = ssm.plan
+        pr = ssm._precision_packed()
+        b = _kf_scratch(cache, pl, ("D", "r", "L", "y", "Sig", "x"))
+        o = sv.o
+        Fmu = torch.empty((ssm.B, ssm.T, o), dtype=torch.float64, device=pl.device)
+        Fvar = torch.empty_like(Fmu)
+        fo = cache.get("factor_of")
+        if fo is not None and fo.matches(keep[0], keep[1], pl.epoch):
+            # elbo() has just factorised exactly this system (same sites, zero-mean prior, nothing else ran on the plan since): the
+            # selected inverse and the projection are all that is left (variational_cvi.py:351-379 calls the two back to back)
+            _lib.check(pl.lib.mfgm_kf_sites_predict_factored(pl.h, ctypes.byref(sv), _ptr(pr["sub"]), _ptr(b["L"]), _ptr(b["y"]), _ptr(b["Sig"]),
+                                                             _ptr(b["x"]), _ptr(Fmu), _ptr(Fvar), _ptr(pl.ws), _stream()),
+                       "mfgm_kf_sites_predict_factored")
+        else:
+            pl.epoch += 1
+            _lib.check(pl.lib.mfgm_kf_sites_predict(pl.h, ctypes.byref(sv), _ptr(pr["diag"]), _ptr(pr["sub"]),
+                                                    None if cache["zero_mean"] else _ptr(pr["lin"]), _ptr(b["D"]), _ptr(b["r"]), _ptr(b["L"]),
+                                                    _ptr(b["y"]), _ptr(b["Sig"]), _ptr(b["x"]), _ptr(Fmu), _ptr(Fvar), _ptr(pl.ws),
+                                                    _ptr(pl.info), _stream()), "mfgm_kf_sites_predict")
+            factored_for(cache, keep, pl)
+        shp = ssm.batch_shape + (ssm.T, o)
+        return Fmu.reshape(shp), Fvar.reshape(shp)
 
-def _predict_f_fused(self):
-    """predict_f at the data points through mfgm_kf_sites_predict (time-invariant emission, state_dim <= 8): assembly, sweeps and the
-    projection onto f in one library call; None when the model does not qualify."""
-    import ctypes
-    from . import _lib
-    from .kalman_filter import _kf_scratch, fused_sites_call
-    from .packed import _ptr, _stream
-    ssm = self.dist_p
-    call = fused_sites_call(ssm, self._emission(), self.sites)
-    if call is None:
-        return None
-    sv, keep, cache = call
-    pl = ssm.plan
-    pr = ssm._precision_packed()
-    b = _kf_scratch(cache, pl, ("D", "r", "L", "y", "Sig", "x"))
-    o = sv.o
-    Fmu = torch.empty((ssm.B, ssm.T, o), dtype=torch.float64, device=pl.device)
-    Fvar = torch.empty_like(Fmu)
-    fo = cache.get("factor_of")
-    if (fo is not None and fo[0] is keep[0] and fo[1] == keep[0]._version and fo[2] is keep[1] and fo[3] == keep[1]._version
-            and fo[4] == pl.epoch):
-        # elbo() has just factorised exactly this system (same sites, zero-mean prior, nothing else ran on the plan since): the
-        # selected inverse and the projection are all that is left (variational_cvi.py:351-379 calls the two back to back)
-        _lib.check(pl.lib.mfgm_kf_sites_predict_factored(pl.h, ctypes.byref(sv), _ptr(pr["sub"]), _ptr(b["L"]), _ptr(b["y"]), _ptr(b["Sig"]),
-                                                         _ptr(b["x"]), _ptr(Fmu), _ptr(Fvar), _ptr(pl.ws), _stream()),
-                   "mfgm_kf_sites_predict_factored")
-    else:
-        pl.epoch += 1
-        _lib.check(pl.lib.mfgm_kf_sites_predict(pl.h, ctypes.byref(sv), _ptr(pr["diag"]), _ptr(pr["sub"]),
-                                                None if cache["zero_mean"] else _ptr(pr["lin"]), _ptr(b["D"]), _ptr(b["r"]), _ptr(b["L"]),
-                                                _ptr(b["y"]), _ptr(b["Sig"]), _ptr(b["x"]), _ptr(Fmu), _ptr(Fvar), _ptr(pl.ws),
-                                                _ptr(pl.info), _stream()), "mfgm_kf_sites_predict")
-        cache["factor_of"] = (keep[0], keep[0]._version, keep[1], keep[1]._version, pl.epoch) if cache["zero_mean"] else None
-    shp = ssm.batch_shape + (ssm.T, o)
-    return Fmu.reshape(shp), Fvar.reshape(shp)
+    def _step_sites(self):
+        """The site tensors update_sites writes: a graph replay writes them behind the host's back (step_graph)."""
+        return self.sites.nat1, self.sites.nat2
 
+    def _step_warm_up(self):
+        """One eager pass over what step_graph captures: scratch, caches and library handles exist before the capture begins."""
+        self.predict_f_at_data()
+        self.elbo()
 
-GaussianProcessWithSitesBase._predict_f_fused = _predict_f_fused
+    def step_graph(self):
+        """`update_sites(); elbo()` -- the inner loop of CVI (variational_cvi.py:351-379) and of PEP over all sites -- captured ONCE in
+        a HIP graph: returns a callable that replays it and hands back the ELBO (a device scalar that every replay overwrites).  On one chain the step is a
+        sequence of ~20 short dependent launches (level sweeps of a few microseconds each): replayed from a graph they cost no host time
+        at all.  The captured order is SELF-CONTAINED: update_sites factorises the system of the current sites itself (it does not
+        take the eager shortcut of reusing the factorisation elbo() left in the plan's scratch -- that decision depends on host-side
+        stamps a replay cannot re-evaluate), and every replay advances those stamps (site versions, plan epoch) and drops the
+        "factorisation belongs to these sites" record, so eager calls and replays can be interleaved in any order."""
+        self._step_warm_up()
+        call = fused_sites_call(self.dist_p, self._emission(), self.sites)
+        cache = call[2] if call is not None else {}
+        cache["factor_of"] = None                   # capture factor + selected inverse + projection, not the shortcut
+        pl = self.dist_p.plan
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self.update_sites()
+            e = self.elbo()
+        cache["factor_of"] = None                   # nothing ran during the capture: the scratch holds no factorisation of these sites
+
+        def step():
+            graph.replay()
+            # the replay moved the sites and overwrote the plan's scratch behind the host's back
+            wrote(*self._step_sites())
+            pl.epoch += 1
+            cache["factor_of"] = None
+            return e
+        step.graph = graph
+        return step
 
 
 class CVIGaussianProcess(GaussianProcessWithSitesBase):
@@ -257,6 +300,11 @@ class CVIGaussianProcess(GaussianProcessWithSitesBase):
         obj = self.local_objective(Fmu, Fvar, self._observations).sum()
         return obj, self._likelihood.ve_gradients_expectation(Fmu, Fvar, self._observations)
 
+    def _step_warm_up(self):
+        fx_mus, fx_covs = self.predict_f_at_data()
+        self._likelihood.ve_gradients_expectation(fx_mus, fx_covs, self._observations)      # (fills the likelihood's gradient cache)
+        self.elbo()
+
     def update_sites(self):
         """theta <- (1 - rho) theta + rho g (variational_cvi.py:351-368)."""
         fx_mus, fx_covs = self.predict_f_at_data()
@@ -268,26 +316,18 @@ class CVIGaussianProcess(GaussianProcessWithSitesBase):
         # (torch._foreach_lerp_ on these two small tensors runs a 25 us multi-tensor kernel: 15 % of the config-2 step)
         n1, n2, g1, g2 = self.sites.nat1, self.sites.nat2, grads[0], grads[1]
         if n1.is_cuda and n1.is_contiguous() and n2.is_contiguous() and g1.shape == n1.shape and g2.numel() == n2.numel():
-            from . import _lib
-            from .packed import _ptr, _stream
             g1, g2 = g1.contiguous(), g2.contiguous()
             _lib.check(_lib.load().mfgm_site_lerp(_ptr(n1), _ptr(g1), n1.numel(), _ptr(n2), _ptr(g2), n2.numel(), float(lr), _stream()),
                        "mfgm_site_lerp")
-            torch.autograd.graph.increment_version(n1)      # written behind torch's back: the factor caches key on ._version
-            torch.autograd.graph.increment_version(n2)
+            wrote(n1, n2)
         else:
             torch._foreach_lerp_([n1, n2], [g1, g2[..., None]], lr)
-
-    def elbo(self):
-        """The marginal likelihood of the model whose likelihood terms are the Gaussian sites (variational_cvi.py:370-379)."""
-        return self.log_likelihood()
 
     def classic_elbo_tape(self, nat1=None, nat2=None):
         """classic_elbo as a differentiable function of the site parameters (leaves of a torch graph; default: detached copies of the
         model's sites with requires_grad) -- the gradient the reference takes with a GradientTape over `trainable_variables` in
         tests/integration/models/test_variational_cvi.py:104-110 (kernel and likelihood frozen there).  Returns (elbo, (nat1, nat2)).
         One chain per batch entry; the posterior naturals  prior + back-projected sites  go through vidp_amd.tape."""
-        from . import tape
         ssm = self.dist_p
         pl, B, T, d = ssm.plan, ssm.B, ssm.T, ssm.d
         if pl.d != d or d > 8:
@@ -314,7 +354,6 @@ class CVIGaussianProcess(GaussianProcessWithSitesBase):
         """classic_elbo as a differentiable function of the KERNEL's hyper-parameters (the sites held fixed): (elbo, leaves) with leaves
         the kernel's hyperparameter_leaves -- what the reference gets from a GradientTape over the kernel's tf.Variables
         (tests/integration/models/test_variational_cvi.py:93-110 with the kernel not frozen).  One chain; d <= 8."""
-        from . import tape
         ssm = self.dist_p
         pl, T, d = ssm.plan, ssm.T, ssm.d
         if ssm.B != 1 or d > 8:
@@ -330,46 +369,6 @@ class CVIGaussianProcess(GaussianProcessWithSitesBase):
         fvar = torch.diagonal(Hb @ cov @ Hb.transpose(-1, -2), dim1=-2, dim2=-1)
         ve = self._likelihood.variational_expectations(fmu, fvar, self._observations.reshape(1, T, -1)).sum()
         return ve - tape.kl_divergence_tape(q, p).sum(), leaves
-
-    def step_graph(self):
-        """`update_sites(); elbo()` -- the inner loop of CVI (variational_cvi.py:351-379) -- captured ONCE in a HIP graph: returns a
-        callable that replays it and hands back the ELBO (a device scalar that every replay overwrites).  On one chain the step is a
-        sequence of ~20 short dependent launches (level sweeps of a few microseconds each): replayed from a graph they cost no host time
-        at all.  The captured order is SELF-CONTAINED: update_sites factorises the system of the current sites itself (it does not
-        take the eager shortcut of reusing the factorisation elbo() left in the plan's scratch -- that decision depends on host-side
-        stamps a replay cannot re-evaluate), and every replay advances those stamps (site versions, plan epoch) and drops the
-        "factorisation belongs to these sites" record, so eager calls and replays can be interleaved in any order."""
-        from .kalman_filter import fused_sites_call
-        fx_mus, fx_covs = self.predict_f_at_data()
-        self._likelihood.ve_gradients_expectation(fx_mus, fx_covs, self._observations)
-        self.elbo()
-        call = fused_sites_call(self.dist_p, self._emission(), self.sites)
-        cache = call[2] if call is not None else {}
-        cache["factor_of"] = None                   # capture factor + selected inverse + projection, not the shortcut
-        pl = self.dist_p.plan
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self.update_sites()
-            e = self.elbo()
-        cache["factor_of"] = None                   # nothing ran during the capture: the scratch holds no factorisation of these sites
-
-        def step():
-            graph.replay()
-            # the replay moved the sites and overwrote the plan's scratch behind the host's back
-            torch.autograd.graph.increment_version(self.sites.nat1)
-            torch.autograd.graph.increment_version(self.sites.nat2)
-            pl.epoch += 1
-            cache["factor_of"] = None
-            return e
-        step.graph = graph
-        return step
-
-    def predict_log_density(self, input_data, full_output_cov=False):
-        """log p(y* | data) per point (variational_cvi.py:406-421): the likelihood's predict_log_density of posterior.predict_f."""
-        X, Y = input_data
-        f_mean, f_var = self.posterior.predict_f(X, full_output_cov=full_output_cov)
-        return self._likelihood.predict_log_density(f_mean, f_var, Y)
 
     def classic_elbo(self):
         """sum_i E_q log p(y_i | f_i) - KL[q(s) || p(s)] (variational_cvi.py:381-404)."""

@@ -16,9 +16,13 @@ import os
 import numpy as np
 import torch
 
+from . import linalg, quad, tape
 from ._lib import FULL, SYM, VEC
 from .packed import CqState, Plan, aligned_segment_length, observation_period
-from .state_space_model import StateSpaceModel
+from .sde import mvnquad
+from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
+from .stamps import Stamp, wrote
+from .state_space_model import PackedSSM, StateSpaceModel
 
 
 def grid_indices(time_grid, obs_times):
@@ -90,8 +94,13 @@ class CVISitesSSM:
             self._path = (pl.pack(VEC, mu.reshape(self.B, self.T, d)), pl.pack(SYM, cov.reshape(self.B, self.T, d, d)))
             self.fx_mus_obs = pl.gather_nodes(VEC, self._path[0], self.obs_node_ids)
             self.fx_covs_obs = pl.gather_nodes(SYM, self._path[1], self.obs_node_ids)
+        # one view object for the model's lifetime: the likelihood stamps its gradient cache on the tensor object and its version
+        self._obs_flat = self._observations.view(self.B * self.n_obs, self.obs_dim)
+        self._theta_p = None
         self._theta_q = None        # dense posterior naturals, allocated when first built
-        self._started = False
+        self._theta_q_valid = False
+        self._started = False       # before the first update the marginals are those of the initial posterior path
+        self._obs_fresh = False     # whether fx_mus_obs / fx_covs_obs hold the marginals of the current sites
         self._bufs = dict(f={}, s={})
         self._q = None          # cached posterior refresh (factor + selected inverse) for the current sites
         self.dist_p = None
@@ -109,7 +118,7 @@ class CVISitesSSM:
         self.dist_p = ssm
         pk = ssm.packed
         nat = self.plan.ssm_to_naturals(pk.A, pk.off, pk.chol, precision=False, want_logdet=True)
-        old_p, had_q = getattr(self, "_theta_p", None), getattr(self, "_theta_q_valid", False)
+        old_p, had_q = self._theta_p, self._theta_q_valid
         self._theta_p = PackedBTDNat(nat["lin"], nat["diag"], nat["sub"])
         if had_q and old_p is not None and move_theta_q:
             # the (implicit) Girsanov sites stay what they are: theta_q moves with the prior
@@ -136,9 +145,13 @@ class CVISitesSSM:
         pl.lincomb(tq.lin, 1.0, tp.lin, 1.0, g.lin)
         pl.lincomb(tq.diag, 1.0, tp.diag, 1.0, g.diag)
         pl.lincomb(tq.sub, 1.0, tp.sub, 1.0, g.sub)
-        pl.scatter_nodes(VEC, tq.lin, self.obs_node_ids, self.data_nat1, accumulate=True)
-        pl.scatter_nodes(SYM, tq.diag, self.obs_node_ids, self.data_nat2, accumulate=True)
+        self._add_data_sites(tq.lin, tq.diag)
         self._theta_q_valid = True
+
+    def _add_data_sites(self, lin, diag, scale=1.0):
+        """(lin, diag) += scale x the data sites scattered to their nodes (packed VEC / SYM arrays, in place)."""
+        self.plan.scatter_nodes(VEC, lin, self.obs_node_ids, self.data_nat1, accumulate=True, scale=scale)
+        self.plan.scatter_nodes(SYM, diag, self.obs_node_ids, self.data_nat2, accumulate=True, scale=scale)
 
     @property
     def girsanov_sites(self):
@@ -146,8 +159,7 @@ class CVISitesSSM:
         pl, tq, tp = self.plan, self.full_sites(), self._theta_p
         g = PackedBTDNat(pl.lincomb(pl.empty(VEC), 1.0, tq.lin, -1.0, tp.lin), pl.lincomb(pl.empty(SYM), 1.0, tq.diag, -1.0, tp.diag),
                          pl.lincomb(pl.empty(FULL), 1.0, tq.sub, -1.0, tp.sub))
-        pl.scatter_nodes(VEC, g.lin, self.obs_node_ids, self.data_nat1, accumulate=True, scale=-1.0)
-        pl.scatter_nodes(SYM, g.diag, self.obs_node_ids, self.data_nat2, accumulate=True, scale=-1.0)
+        self._add_data_sites(g.lin, g.diag, scale=-1.0)
         return g
 
     def full_sites(self):
@@ -155,7 +167,7 @@ class CVISitesSSM:
         The posterior natural parameters theta_q (variational_cvi_sde.py:161-174).  They are kept resident and
         updated incrementally by the site updates instead of being re-summed on every access.
         """
-        if not getattr(self, "_theta_q_valid", False):
+        if not self._theta_q_valid:
             self._rebuild_theta_q()
         return self._theta_q
 
@@ -206,7 +218,6 @@ class CVISitesSSM:
     @property
     def dist_q(self) -> StateSpaceModel:
         """The posterior as a StateSpaceModel (variational_cvi_sde.py:177-192), via naturals_to_ssm_params."""
-        from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
         tq = self.full_sites()
         return naturals_to_ssm_params_packed(self.plan, tq.lin, tq.diag, tq.sub)
 
@@ -226,15 +237,16 @@ class CVISitesSSM:
         return self.plan.unpack(SYM, self._refresh(want_marginals=True)["Sig"])
 
     # -- updates -------------------------------------------------------------------------------------------
-    def _obs_flat(self):
-        # one view object for the model's lifetime: the likelihood keys its gradient cache on the tensor object and its version
-        if getattr(self, "_obs_flat_view", None) is None:
-            self._obs_flat_view = self._observations.view(self.B * self.n_obs, self.obs_dim)
-        return self._obs_flat_view
+    def _sites_moved(self):
+        """The sites (hence the posterior) changed: nothing computed from the previous ones is current, and the marginals are those
+        of the sites from now on, no longer those of the initial posterior path."""
+        self._q = None
+        self._obs_fresh = False   # marginals at the observation times are gathered lazily, when next needed
+        self._started = True
 
     def _obs_marginals(self):
         """(mu, Sigma) at the observation times for the current sites (the reference's self.fx_mus / fx_covs gathered)."""
-        if self._started and not getattr(self, "_obs_fresh", False):
+        if self._started and not self._obs_fresh:
             self._gather_obs()
         return self.fx_mus_obs, self.fx_covs_obs
 
@@ -259,19 +271,16 @@ class CVISitesSSM:
             if self._started:
                 # the marginals are read from the packed arrays of the refresh at the observation nodes (no gather first)
                 q = self._refresh(want_marginals=True)
-                self.plan.readout_site_update(rd, q["mu"], q["Sig"], self.obs_node_ids, self._obs_flat(), tq.lin, tq.diag, self.data_nat1,
+                self.plan.readout_site_update(rd, q["mu"], q["Sig"], self.obs_node_ids, self._obs_flat, tq.lin, tq.diag, self.data_nat1,
                                               self.data_nat2, lr)
             else:
                 # before the first update the marginals are those of the initial posterior path, gathered at construction
-                self.plan.readout_site_update(rd, self.fx_mus_obs, self.fx_covs_obs, self.obs_node_ids, self._obs_flat(), tq.lin, tq.diag,
+                self.plan.readout_site_update(rd, self.fx_mus_obs, self.fx_covs_obs, self.obs_node_ids, self._obs_flat, tq.lin, tq.diag,
                                               self.data_nat1, self.data_nat2, lr, gathered=True)
-            self._started = True
-            self._q = None
-            self._obs_fresh = False
+            self._sites_moved()
             return
-        mu_o, cov_o = self._obs_marginals()
-        self._started = True      # before the first update the marginals are those of the initial posterior path
-        g1, g2 = self.likelihood.ve_gradients_expectation(mu_o, cov_o, self._obs_flat())
+        mu_o, cov_o = self._obs_marginals()      # before the first update: those of the initial posterior path
+        g1, g2 = self.likelihood.ve_gradients_expectation(mu_o, cov_o, self._obs_flat)
         tq = self.full_sites()
         if (self.fused_obs_kernels and self.plan.d <= 8 and g1.shape == self.data_nat1.shape and g2.shape == self.data_nat2.shape
                 and self.data_nat1.is_contiguous() and self.data_nat2.is_contiguous()):
@@ -284,8 +293,7 @@ class CVISitesSSM:
             self.plan.scatter_nodes_pair(tq.lin, tq.diag, self.obs_node_ids, new1 - self.data_nat1, new2 - self.data_nat2)
             self.data_nat1.copy_(new1)
             self.data_nat2.copy_(new2)
-        self._q = None
-        self._obs_fresh = False   # marginals at the observation times are gathered lazily, when next needed
+        self._sites_moved()
 
     def grad_kl_wrt_exp_param(self):
         """
@@ -306,9 +314,7 @@ class CVISitesSSM:
         for qq, pp in ((tq.lin, tp.lin), (tq.diag, tp.diag), (tq.sub, tp.sub)):
             pl.lincomb(qq, 1.0 - lr, qq, lr, pp)               # theta_q += lr (theta_p - theta_q)
         pl.scatter_nodes_pair(tq.lin, tq.diag, self.obs_node_ids, self.data_nat1, self.data_nat2, scale=lr)
-        self._q = None
-        self._obs_fresh = False
-        self._started = True
+        self._sites_moved()
 
     # -- objective -----------------------------------------------------------------------------------------
     def variational_expectation(self):
@@ -318,7 +324,7 @@ class CVISitesSSM:
             # multivariate Gaussian likelihood: gather, element-wise arithmetic and per-trajectory sum in one launch (it also
             # refreshes the gathered marginals)
             q = self._refresh()
-            ve = self.plan.mvn_obs_ve(q["mu"], q["Sig"], self.obs_node_ids, self.n_obs, self._obs_flat(), lik.inv_covariance,
+            ve = self.plan.mvn_obs_ve(q["mu"], q["Sig"], self.obs_node_ids, self.n_obs, self._obs_flat, lik.inv_covariance,
                                       lik.ve_constant, out_mu=self.fx_mus_obs, out_cov=self.fx_covs_obs)
             self._obs_fresh = True
             return ve
@@ -326,13 +332,13 @@ class CVISitesSSM:
         if rd is not None:
             # projections, per-output expectations and per-trajectory sum in one launch (it also refreshes the gathered marginals)
             q = self._refresh(want_marginals=True)
-            ve = self.plan.readout_obs_ve(rd, q["mu"], q["Sig"], self.obs_node_ids, self.n_obs, self._obs_flat(), out_mu=self.fx_mus_obs,
+            ve = self.plan.readout_obs_ve(rd, q["mu"], q["Sig"], self.obs_node_ids, self.n_obs, self._obs_flat, out_mu=self.fx_mus_obs,
                                           out_cov=self.fx_covs_obs)
             self._obs_fresh = True
             return ve
-        if self._q is None or not getattr(self, "_obs_fresh", False):
+        if self._q is None or not self._obs_fresh:
             self._gather_obs()
-        ve = lik.variational_expectations(self.fx_mus_obs, self.fx_covs_obs, self._obs_flat())
+        ve = lik.variational_expectations(self.fx_mus_obs, self.fx_covs_obs, self._obs_flat)
         return ve.reshape(self.B, self.n_obs).sum(-1)
 
     def KL_q_p(self):
@@ -352,6 +358,64 @@ class CVISitesSSM:
         return self.classic_elbo_per_trajectory().sum()
 
 
+class _Ahead:
+    """What CVISitesSDE's pipelining across steps keeps between calls: the learning rate the prediction assumes (that of the last
+    update_data_sites), the two spare site buffers (they hold the predicted sites), the optional side stream and the record itself --
+    the stamp of the state it was made FOR and, once update_data_sites has taken the prediction over, the stamp of the state the
+    separator system in the plan's workspace is armed for.  Every stamp is over (site_lin, site_sym, cq, cq.version, lr, plan.epoch):
+    a site written or replaced, a Girsanov update, another learning rate or another factorisation on the plan leaves no match.
+    Host bookkeeping only: the launches are the caller's (`make` is handed them as a callable)."""
+
+    def __init__(self):
+        self.lr, self.bufs, self.side = None, None, None
+        self.rec = None         # [stamp made for, stamp armed for | None]
+        self.consumed = 0       # records taken over by update_data_sites so far
+
+    def _parts(self, lin, sym, cq, plan, lr):
+        return lin, sym, cq, cq.version, float(lr), plan.epoch
+
+    def make(self, lin, cq, plan, launch):
+        """Record for the state as it is now: launch(spare_lin, spare_sym, lr) writes the predicted sites and runs the factorisation
+        that makes their separator system beside its own work; its result is handed back."""
+        self.drop()
+        if self.bufs is None:
+            self.bufs = [torch.empty_like(lin), torch.empty_like(cq.site_sym)]
+        out = launch(self.bufs[0], self.bufs[1], self.lr)
+        self.rec = [Stamp(*self._parts(lin, cq.site_sym, cq, plan, self.lr)), None]
+        return out
+
+    def accept(self, lr, lin, cq, plan):
+        """update_data_sites(lr) on sites (lin, cq.site_sym): the predicted (lin, sym) to exchange them for when the record was made
+        for exactly this blend (the former site arrays become the spare buffers); else None, and the record is dropped."""
+        rec, out, self.lr = self.rec, None, float(lr)
+        if rec is not None and rec[0].matches(*self._parts(lin, cq.site_sym, cq, plan, lr)):
+            self.bufs, out = [lin, cq.site_sym], tuple(self.bufs)
+            rec[1] = Stamp(*self._parts(out[0], out[1], cq, plan, lr))
+            self.consumed += 1
+        else:
+            self.drop()
+        return out
+
+    def take(self, lin, cq, plan):
+        """Whether a separator system was made ahead for the state as it is NOW: consumed by the next factorisation (which joins the
+        side stream itself)."""
+        rec = self.rec
+        if rec is None:
+            return False
+        if rec[1] is None or not rec[1].matches(*self._parts(lin, cq.site_sym, cq, plan, self.lr)):
+            self.drop()
+            return False
+        self.rec = None
+        return True
+
+    def drop(self):
+        """Forget the record (the stream it was made on is joined first: its buffers are about to be reused)."""
+        if self.rec is not None:
+            if self.side is not None:
+                torch.cuda.current_stream().wait_stream(self.side)
+            self.rec = None
+
+
 class CVISitesSDE(CVISitesSSM):
     """
     CVI-DP (variational_cvi_sde.py:368-518): non-linear SDE prior, linearised along the current posterior path;
@@ -368,7 +432,11 @@ class CVISitesSDE(CVISitesSSM):
             prior_initial_state = (torch.zeros(d, dtype=torch.float64).numpy(), q * (torch.ones((d, d), dtype=torch.float64).numpy()))
         self.stabilize_ssm = stabilize_ssm
         self.clip_state_transitions = clip_state_transitions
+        # (set before the base constructor runs: it assigns the data sites, whose setters look at the structured state)
         self._cq, self._cq_off, self._cq_dense, self._cq_p0_moved = None, False, None, False
+        self._sde_prm, self._theta_spare = None, None
+        self._ahead = _Ahead()
+        self._cq_g2 = (None, None)      # (the likelihood's nat2 gradient, its one block in packed form)
         super().__init__(None, time_grid, input_data, likelihood, prior_initial_state=prior_initial_state,
                          initial_posterior_path=initial_posterior_path, plan=plan)
         self._sde_prm = prior_sde.params(self.dt, prior_initial_state[0], prior_initial_state[1])
@@ -438,9 +506,27 @@ class CVISitesSDE(CVISitesSSM):
 
     @data_nat2.setter
     def data_nat2(self, value):
-        if getattr(self, "_cq", None) is not None:
+        if self._cq is not None:
             self._cq_leave()
         self._data_nat2 = value
+
+    @property
+    def data_nat1(self):
+        """Data-site nat1, [B n_obs, d].  Assigning a tensor makes it the site array (in cq mode the sweeps read it from then on) and
+        drops what was computed from the previous one.  On the dense route the sites are summed into theta_q, which the caller has
+        to rebuild after assigning sites by hand (as exp_io.load_cvi_model does)."""
+        return self._data_nat1
+
+    @data_nat1.setter
+    def data_nat1(self, value):
+        self._data_nat1 = value
+        if self._cq is not None:
+            self._cq.site_lin = value
+            self._sites_moved()
+
+    def _sites_moved(self):
+        super()._sites_moved()
+        self._cq_dense = None
 
     def _sym_full(self, packed):
         d = self.state_dim
@@ -486,22 +572,16 @@ class CVISitesSDE(CVISitesSSM):
         self._theta_q = None          # the dense arrays are materialised on demand only
         return True
 
-    def _cq_dense_free(self):
-        """Dense packed (lin, diag, sub) of theta_prior + Girsanov sites (no data sites) from the cq state."""
-        return self.plan.cq_unpack(self._cq)
-
-    def _cq_leave(self):
-        """Back to the dense arrays (a caller assigned sites the structured state cannot hold)."""
-        cq, pl = self._cq, self.plan
-        lin, diag, sub = self._cq_dense_free()
-        if cq.site_sym is not None:
-            self._data_nat2 = self._sym_full(cq.site_sym).expand(self.B * self.n_obs, -1, -1).contiguous()
+    def _cq_leave(self, data_sites=True):
+        """Back to the dense arrays (a caller assigned sites the structured state cannot hold); data_sites=False leaves the data sites
+        out of them (theta_prior + Girsanov sites alone)."""
+        lin, diag, sub = self.plan.cq_unpack(self._cq)      # theta_prior + Girsanov sites, dense packed (no data sites)
+        if self._cq.site_sym is not None:
+            self._data_nat2 = self.data_nat2                # (the one shared block, expanded)
         self._cq, self._cq_dense = None, None
-        if self._data_nat2.numel():
-            pl.scatter_nodes(VEC, lin, self.obs_node_ids, self.data_nat1, accumulate=True)
-            pl.scatter_nodes(SYM, diag, self.obs_node_ids, self._data_nat2, accumulate=True)
-        self._theta_q = PackedBTDNat(lin, diag, sub)
-        self._theta_q_valid = True
+        if data_sites and self._data_nat2.numel():
+            self._add_data_sites(lin, diag)
+        self._theta_q, self._theta_q_valid = PackedBTDNat(lin, diag, sub), True
 
     def _rebuild_theta_q(self, g=None):
         """theta_q from the prior, the Girsanov sites `g` (default: the initial ones) and the data sites; into the cq state when the
@@ -517,29 +597,26 @@ class CVISitesSDE(CVISitesSSM):
                             pl.lincomb(pl.empty(FULL), 1.0, tp.sub, 1.0, g.sub))
         if self._cq_try_enter(free.lin, free.diag, free.sub):
             return
-        pl.scatter_nodes(VEC, free.lin, self.obs_node_ids, self.data_nat1, accumulate=True)
-        pl.scatter_nodes(SYM, free.diag, self.obs_node_ids, self._data_nat2, accumulate=True)
+        self._add_data_sites(free.lin, free.diag)
         self._theta_q, self._theta_q_valid = free, True
 
     def full_sites(self):
         """The posterior natural parameters theta_q, dense and packed (variational_cvi_sde.py:161-174); in cq mode they are
         materialised from the structured state (and cached until the next update)."""
-        if not getattr(self, "_theta_q_valid", False):
+        if not self._theta_q_valid:
             self._rebuild_theta_q()
         if self._cq is None:
             return self._theta_q
         if self._cq_dense is None:
-            pl = self.plan
-            lin, diag, sub = self._cq_dense_free()
+            lin, diag, sub = self.plan.cq_unpack(self._cq)      # theta_prior + Girsanov sites, dense packed (no data sites)
             if self._cq.slot is not None:
-                pl.scatter_nodes(VEC, lin, self.obs_node_ids, self.data_nat1, accumulate=True)
-                pl.scatter_nodes(SYM, diag, self.obs_node_ids, self.data_nat2, accumulate=True)
+                self._add_data_sites(lin, diag)
             self._cq_dense = PackedBTDNat(lin, diag, sub)
         return self._cq_dense
 
     def _cq_state(self):
         """The cq state, built on first use; None when the model runs on the dense arrays."""
-        if not getattr(self, "_theta_q_valid", False):
+        if not self._theta_q_valid:
             self._rebuild_theta_q()
         return self._cq
 
@@ -554,17 +631,13 @@ class CVISitesSDE(CVISitesSSM):
             self._theta_q_valid = True
             return
         # theta_q follows the prior: through the dense data-free arrays (a rare call: prior-parameter gradients)
-        lin, diag, sub = self._cq_dense_free()
-        if cq.site_sym is not None:
-            self._data_nat2 = self._sym_full(cq.site_sym).expand(self.B * self.n_obs, -1, -1).contiguous()
-        self._theta_q, self._theta_q_valid, self._cq, self._cq_dense = PackedBTDNat(lin, diag, sub), True, None, None
+        self._cq_leave(data_sites=False)
         super()._set_prior(ssm, move_theta_q=True)
         tq = self._theta_q
         keep_sites = (cq.slot, cq.site_lin, cq.site_sym)
         if not self._cq_try_enter(tq.lin, tq.diag, tq.sub):
             if self._data_nat2.numel():
-                self.plan.scatter_nodes(VEC, tq.lin, self.obs_node_ids, self.data_nat1, accumulate=True)
-                self.plan.scatter_nodes(SYM, tq.diag, self.obs_node_ids, self._data_nat2, accumulate=True)
+                self._add_data_sites(tq.lin, tq.diag)
             self._theta_q, self._theta_q_valid = tq, True
         else:
             self._cq.slot, self._cq.site_lin, self._cq.site_sym = keep_sites
@@ -574,7 +647,7 @@ class CVISitesSDE(CVISitesSSM):
     fused_girsanov = os.environ.get("VIDP_FUSED_GIRSANOV", "1") != "0"
 
     def _sweep_fusion(self):
-        pl, prm = self.plan, getattr(self, "_sde_prm", None)
+        pl, prm = self.plan, self._sde_prm
         return self.fused_girsanov and prm is not None and pl.d <= 8 and pl.nlevels >= 2 and prm.kind == 0
 
     _need_sub = False    # the closed-form SDE KL needs only (mu, diag Sigma, diag Sigma_sub): the moment array
@@ -584,10 +657,10 @@ class CVISitesSDE(CVISitesSSM):
     # ends up with do not depend on q, so the state the FIRST factorisation of the next step will see (dyn as it is after this step's
     # Girsanov update, the sites one more blend ahead) is known while this step's SECOND factorisation runs: its level-0 reduce -- an
     # arithmetic-bound kernel on 18 doubles per node -- is launched on a second stream next to that factorisation's bandwidth-bound
-    # forward sweep (Plan.cq_factor(next_sites=...)), and the next step starts from the separator system it left.  The prediction
-    # assumes the learning rate of the last update_data_sites; it is keyed on the identity / version of the cq state and of the site
-    # tensors, and anything that does not match (another learning rate, a re-linearisation, sites assigned by hand) simply finds no
-    # record and runs the reduce itself.  Results are bit-identical either way (the record holds the numbers the reduce would write).
+    # forward sweep (Plan.cq_factor(next_sites=...)), and the next step starts from the separator system it left.  The record of what
+    # was made ahead, and for which state, is `self._ahead` (_Ahead): anything that does not match its stamp (another learning rate, a
+    # re-linearisation, sites assigned by hand) simply finds no record and runs the reduce itself.  Results are bit-identical either
+    # way (the record holds the numbers the reduce would write).
     pipelined = os.environ.get("VIDP_PIPELINE", "1") != "0"
     # VIDP_PIPE_STREAMS=1: the reduce made ahead runs as a kernel of its own on a second stream (round 4's first form; A/B) instead of
     # as the second wavefront of the forward sweep's workgroups (k_forward_reduce_cq: the records are read once)
@@ -595,34 +668,13 @@ class CVISitesSDE(CVISitesSSM):
     # below this many nodes (B T) a level-0 reduce is a few microseconds: the second stream's event round trips would cost more than
     # they hide (config 1, T = 1001: 0.133 -> 0.174 ms with it)
     pipeline_min_nodes = 200000
-    _pre = None           # the record of a separator system made ahead (dict), None when there is none
 
-    def _pipe_sites_gradient(self):
-        g1, g2 = self.likelihood.ve_gradients_expectation(self.fx_mus_obs, self.fx_covs_obs, self._obs_flat())
-        if getattr(self, "_cq_g2", (None,))[0] is not g2:
+    def _site_blend(self, cq, lin, sym, lr):
+        """(lin, sym) <- (1 - lr) site + lr gradient (variational_cvi_sde.py:301-317), both site arrays in one launch."""
+        g1, g2 = self.likelihood.ve_gradients_expectation(self.fx_mus_obs, self.fx_covs_obs, self._obs_flat)
+        if self._cq_g2[0] is not g2:
             self._cq_g2 = (g2, self._sym_packed(g2[0]))
-        return g1, self._cq_g2[1]
-
-    _pipe_side = None     # the second stream of the two-stream form
-
-    def _pipe_drop(self):
-        """Forget a separator system made ahead (the stream it was made on is joined first: its buffers are about to be reused)."""
-        if getattr(self, "_pre", None) is not None:
-            if self._pipe_side is not None:
-                torch.cuda.current_stream().wait_stream(self._pipe_side)
-            self._pre = None
-
-    def _pipe_predict(self, cq):
-        """(site_lin, site_sym) as the next update_data_sites(self._pipe_lr) will leave them, into the model's two spare buffers (one
-        launch; update_data_sites then takes them over by exchanging the buffers)."""
-        g1, g2p = self._pipe_sites_gradient()
-        if getattr(self, "_pipe_bufs", None) is None:
-            self._pipe_bufs = [torch.empty_like(self.data_nat1), torch.empty_like(cq.site_sym)]
-            if self.pipe_two_streams:
-                self._pipe_side = torch.cuda.Stream(device=self.device)
-        lin, sym = self._pipe_bufs
-        self.plan.site_lerp_to(lin, self.data_nat1, g1.contiguous(), sym, cq.site_sym, g2p, self._pipe_lr)
-        return lin, sym
+        self.plan.site_lerp_to(lin, self._data_nat1, g1.contiguous(), sym, cq.site_sym, self._cq_g2[1], lr)
 
     def update_data_sites(self, lr: float):
         cq = self._cq_state()
@@ -630,26 +682,17 @@ class CVISitesSDE(CVISitesSSM):
             return super().update_data_sites(lr)
         # the site gradient of such a likelihood does not depend on the marginals: only the small site arrays move, and the sweeps
         # read them where they need them (no scatter into per-node arrays)
-        self._started = True
-        pre = self._pre
-        if (pre is not None and pre["lr"] == float(lr) and pre["cq"] is cq and pre["ver"] == cq.version
-                and pre["v1"] == (id(self.data_nat1), self.data_nat1._version) and pre["v2"] == (id(cq.site_sym), cq.site_sym._version)):
+        taken = self._ahead.accept(lr, self._data_nat1, cq, self.plan)
+        if taken is not None:
             # exactly the blend the last ELBO refresh predicted (same inputs, same learning rate): its result is taken over -- the
             # site arrays exchange roles with the spare buffers it was written to -- and the separator system of the state it gives
             # is already being made
-            self._pipe_bufs = [self.data_nat1, cq.site_sym]
-            self.data_nat1, cq.site_sym = pre["lin"], pre["sym"]
-            cq.site_lin = self.data_nat1
-            pre["armed"] = (id(self.data_nat1), self.data_nat1._version, id(cq.site_sym), cq.site_sym._version)
+            self._data_nat1, cq.site_sym = taken
+            cq.site_lin = self._data_nat1
         else:
-            self._pipe_drop()
-            g1, g2p = self._pipe_sites_gradient()
-            # (1 - lr) site + lr gradient (variational_cvi_sde.py:301-317), both site arrays in one launch
-            self.plan.site_lerp_to(self.data_nat1, self.data_nat1, g1.contiguous(), cq.site_sym, cq.site_sym, g2p, lr)
-            torch.autograd.graph.increment_version(self.data_nat1)      # written behind torch's back
-            torch.autograd.graph.increment_version(cq.site_sym)
-        self._pipe_lr = float(lr)
-        self._q, self._cq_dense, self._obs_fresh = None, None, False
+            self._site_blend(cq, self._data_nat1, cq.site_sym, lr)
+            wrote(self._data_nat1, cq.site_sym)
+        self._sites_moved()
 
     def snapshot(self):
         """Everything update_data_sites / update_girsanov_sites move, copied: the checkpoint a trainer that synchronises the host once
@@ -664,7 +707,7 @@ class CVISitesSDE(CVISitesSSM):
                     started=self._started)
 
     def restore(self, snap):
-        self._pipe_drop()
+        self._ahead.drop()
         if snap["kind"] == "cq":
             cq = snap["cq"]
             if self._cq is not cq:
@@ -683,21 +726,8 @@ class CVISitesSDE(CVISitesSSM):
                 dst.copy_(src)
             self.data_nat1.copy_(snap["lin"])
             self.data_nat2.copy_(snap["n2"])
+        self._sites_moved()
         self._started = snap["started"]
-        self._q, self._cq_dense, self._obs_fresh = None, None, False
-
-    def _pipe_take(self, cq):
-        """Whether a separator system was made ahead for the state as it is NOW: consumed by the next factorisation."""
-        pre = getattr(self, "_pre", None)
-        if pre is None:
-            return False
-        ok = (pre.get("armed") == (id(self.data_nat1), self.data_nat1._version, id(cq.site_sym), cq.site_sym._version)
-              and pre["cq"] is cq and pre["ver"] == cq.version)
-        if not ok or pre["epoch"] != self.plan.epoch:      # (another factorisation on the plan may have used the workspace since)
-            self._pipe_drop()
-            return False
-        self._pre = None          # the consuming call joins the side stream itself
-        return True
 
     def _refresh(self, want_sub=None, want_mom=None, want_marginals=False):
         """want_marginals: the full marginal arrays (mu, Sig) are wanted.  The ELBO / site-update loop needs only the KL sum and the
@@ -711,19 +741,20 @@ class CVISitesSDE(CVISitesSSM):
         obs = cq.slot is not None
         lazy = obs and not want_marginals and os.environ.get("VIDP_LAZY_MARGINALS", "1") != "0"
         if self._q is None:
-            nxt = None
-            if (self.pipelined and obs and getattr(self, "_pipe_lr", None) is not None and self._sde_prm.kind == 0
+            ahead = self._ahead
+            if (self.pipelined and obs and ahead.lr is not None and self._sde_prm.kind == 0
                     and self.B * self.T >= self.pipeline_min_nodes and self.state_dim <= 6):      # (d = 7, 8: the kernel pair does not fit)
-                # the level-0 reduce of the next step's first factorisation rides next to this factorisation's forward sweep
-                self._pipe_drop()
-                lin, sym = self._pipe_predict(cq)
-                nxt = dict(lr=self._pipe_lr, cq=cq, ver=cq.version, v1=(id(self.data_nat1), self.data_nat1._version),
-                           v2=(id(cq.site_sym), cq.site_sym._version), lin=lin, sym=sym)
-            f = pl.cq_factor(cq, want_logdet=True, out=self._bufs["f"], use_ahead=self._pipe_take(cq) if nxt is None else False,
-                             next_sites=(nxt["lin"], nxt["sym"]) if nxt else None, side=self._pipe_side)
-            if nxt is not None:
-                nxt["epoch"] = pl.epoch
-            self._pre = nxt
+                # the level-0 reduce of the next step's first factorisation rides next to this factorisation's forward sweep: the
+                # sites as the next update_data_sites(ahead.lr) will leave them go into the spare buffers (one launch)
+                if self.pipe_two_streams and ahead.side is None:
+                    ahead.side = torch.cuda.Stream(device=self.device)
+
+                def launch(lin, sym, lr_next):
+                    self._site_blend(cq, lin, sym, lr_next)
+                    return pl.cq_factor(cq, want_logdet=True, out=self._bufs["f"], next_sites=(lin, sym), side=ahead.side)
+                f = ahead.make(self._data_nat1, cq, pl, launch)
+            else:
+                f = pl.cq_factor(cq, want_logdet=True, out=self._bufs["f"], use_ahead=ahead.take(self._data_nat1, cq, pl), side=ahead.side)
             self._bufs["f"].update(L=f["L"], y=f["y"])
             s = pl.cq_selinv_kl(cq, f["L"], f["y"], self._sde_prm, out=self._bufs["s"], obs_mu=self.fx_mus_obs if obs else None,
                                 obs_cov=self.fx_covs_obs if obs else None, want_marginals=not lazy)
@@ -749,9 +780,9 @@ class CVISitesSDE(CVISitesSSM):
         if cq is None or cq.slot is None:
             return super().variational_expectation()
         self._refresh()
-        if not getattr(self, "_obs_fresh", False):
+        if not self._obs_fresh:
             self._gather_obs()
-        return self.plan.mvn_ve_compact(self.fx_mus_obs, self.fx_covs_obs, self.n_obs, self._obs_flat(), lik.inv_covariance, lik.ve_constant,
+        return self.plan.mvn_ve_compact(self.fx_mus_obs, self.fx_covs_obs, self.n_obs, self._obs_flat, lik.inv_covariance, lik.ve_constant,
                                         partials=partials)
 
     def _cq_elbo(self):
@@ -881,7 +912,6 @@ class CVISitesSDE(CVISitesSSM):
         posterior refreshes per parameter), kept as a cross-check.  Like the reference's, the call leaves the prior re-linearised at
         the current posterior.
         """
-        from . import tape
         sde, pl = self.prior_sde, self.plan
         q = self._refresh(want_marginals=True)
         path = (q["mu"].clone(), q["Sig"].clone())
@@ -916,7 +946,7 @@ class CVISitesSDE(CVISitesSSM):
         tq = self.full_sites()
         diag, sub = pl.unpack(SYM, tq.diag), pl.unpack(FULL, tq.sub, T - 1)
         mu_o, cov_o = self._obs_marginals()
-        g1, g2 = self.likelihood.ve_gradients_expectation(mu_o, cov_o, self._obs_flat())
+        g1, g2 = self.likelihood.ve_gradients_expectation(mu_o, cov_o, self._obs_flat)
         g_lin = torch.zeros((B * T, d), dtype=torch.float64, device=self.device).index_add_(0, self.obs_node_ids, g1.reshape(-1, d))
         g_diag = torch.zeros((B * T, d, d), dtype=torch.float64, device=self.device).index_add_(0, self.obs_node_ids, g2.reshape(-1, d, d))
         u = tape.fisher_vector_product(pl, diag, sub, mu, cov, csub, g_lin.view(B, T, d), g_diag.view(B, T, d, d), torch.zeros_like(sub))
@@ -945,7 +975,8 @@ class CVISitesSDE(CVISitesSSM):
         if cq is not None:
             # reduce -> forward -> backward sweep that writes (1 - lr) dyn + lr theta~ into the spare buffer; the uniform off-diagonals
             # scale by (1 - lr); the data sites do not enter (they are not part of the resident state)
-            f = pl.cq_factor(cq, want_logdet=False, out=self._bufs["f"], use_ahead=self._pipe_take(cq), side=self._pipe_side)
+            f = pl.cq_factor(cq, want_logdet=False, out=self._bufs["f"], use_ahead=self._ahead.take(self._data_nat1, cq, pl),
+                             side=self._ahead.side)
             self._bufs["f"].update(L=f["L"], y=f["y"])
             if cq.spare is None:
                 cq.spare = torch.empty_like(cq.dyn)
@@ -960,7 +991,7 @@ class CVISitesSDE(CVISitesSSM):
                                                     dtype=torch.float64, device=self.device))
                 tgt = -0.5 * (P0inv - torch.diag(torch.diagonal(P0inv)))
                 cq.p0_off.lerp_(self._sym_packed(tgt), lr)
-            self._q, self._cq_dense, self._obs_fresh, self._started = None, None, False, True
+            self._sites_moved()
             return
         tq = self.full_sites()
         if (self._q is None or self._q["mom"] is None) and self._sweep_fusion():
@@ -968,7 +999,7 @@ class CVISitesSDE(CVISitesSSM):
             # writing the marginals (mfgm_girsanov.h); theta_q moves to the spare buffer
             f = pl.factor(tq.diag, tq.sub, tq.lin, aD=-2.0, aS=-1.0, aR=1.0, want_logdet=False, out=self._bufs["f"], store_G=False)
             self._bufs["f"].update(L=f["L"], y=f["y"])
-            if getattr(self, "_theta_spare", None) is None:
+            if self._theta_spare is None:
                 self._theta_spare = PackedBTDNat(pl.zeros(VEC), pl.zeros(SYM), pl.zeros(FULL))
             sp = self._theta_spare
             pl.selinv_girsanov(f["L"], tq.sub, -1.0, f["y"], self._sde_prm, (tq.lin, tq.diag, tq.sub), (sp.lin, sp.diag, sp.sub))
@@ -978,9 +1009,7 @@ class CVISitesSDE(CVISitesSSM):
             q = self._refresh(want_mom=True)
             pl.sde_lean(self._sde_prm, q["mom"], mode=3, theta_q=(tq.lin, tq.diag, tq.sub))
         pl.scatter_nodes_pair(tq.lin, tq.diag, self.obs_node_ids, self.data_nat1, self.data_nat2, scale=lr)
-        self._q = None
-        self._obs_fresh = False
-        self._started = True
+        self._sites_moved()
 
 
 class CVISitesSDEQuadrature(CVISitesSSM):
@@ -1037,17 +1066,14 @@ class CVISitesSDEQuadrature(CVISitesSSM):
         """A_k = I + dt E_q[df/dx], b_k = dt (E_q f - E_q[df/dx] m), Q_k = dt q on the current path (sde_utils.py:119-179;
         LinearDrift.to_ssm, drift.py:66-117), installed as dist_p; stabilised: transitions and offsets clipped
         (variational_cvi_sde.py:420-432)."""
-        from . import linalg
         sde, d, dt = self.prior_sde, self.state_dim, self.dt
         mu, cov = self._path_natural()
         # transition k is linearised on the marginal at k + 1, as the reference hands `fx_mus[1:]` to linearize_sde (:412)
         m = mu[:, 1:]
         if self.native:
-            from . import quad
             A, b = quad.linearize(self._quad_prm(), m, cov[:, 1:])
         else:
             chol = linalg.cholesky(cov[:, 1:].contiguous())
-            from .sde import mvnquad
             with torch.no_grad():
                 if hasattr(sde, "expected_drift"):
                     Ef = sde.expected_drift(m, chol)
@@ -1081,8 +1107,6 @@ class CVISitesSDEQuadrature(CVISitesSSM):
     def _kl_from_expectations(self, e1, ed, es):
         """The scalar SDE_SSM_KL_with_grads_wrt_exp_params differentiates (sde_utils.py:496-543), per chain [B], as a torch graph of the
         expectation parameters (e1 [B,T,d], ed [B,T,d,d], es [B,T-1,d,d])."""
-        from . import linalg, tape
-        from .sde import mvnquad
         sde, d, dt = self.prior_sde, self.state_dim, self.dt
         A, b, cP0, cQ, mu0 = tape.expectations_to_ssm_params(e1, ed, es)
         cov = ed - e1[..., :, None] * e1[..., None, :]
@@ -1119,7 +1143,6 @@ class CVISitesSDEQuadrature(CVISitesSSM):
 
     def KL_q_p(self):
         if self.native:
-            from . import quad
             return quad.kl(self._quad_prm(), *self._marginals_natural())
         with torch.no_grad():
             return self._kl_from_expectations(*self._expectations_natural())
@@ -1127,7 +1150,6 @@ class CVISitesSDEQuadrature(CVISitesSSM):
     def grad_KL_wrt_prior_params(self):
         """d KL[q || p_SDE] / d (trainable drift parameters), summed over the trajectories, in `trainable_variables` order
         (variational_cvi_sde.py:495-506); a parameter that is a vector (the network's weights) gets a vector."""
-        from . import quad
         sde = self.prior_sde
         _, gth = quad.kl(self._quad_prm(), *self._marginals_natural(), param_grad=True)
         g = gth.sum(0).cpu().numpy()
@@ -1141,7 +1163,6 @@ class CVISitesSDEQuadrature(CVISitesSSM):
         (variational_cvi_sde.py:508-518), as CVISitesSDE.grad_VE_wrt_prior_params: ONE exact Fisher-vector product F_q g serves every
         parameter, contracted with d theta_p / d kappa of the local linearisation map on the fixed path (a fourth-order central
         difference of the quadrature kernel's linearisation; the map is smooth in the drift parameters)."""
-        from . import quad, tape
         sde, pl = self.prior_sde, self.plan
         T, d, B = self.T, self.state_dim, self.B
         mu0, cov0 = self._path_natural()
@@ -1153,7 +1174,7 @@ class CVISitesSDEQuadrature(CVISitesSSM):
         tq = self.full_sites()
         diag, sub = pl.unpack(SYM, tq.diag), pl.unpack(FULL, tq.sub, T - 1)
         mu_o, cov_o = self._obs_marginals()
-        g1, g2 = self.likelihood.ve_gradients_expectation(mu_o, cov_o, self._obs_flat())
+        g1, g2 = self.likelihood.ve_gradients_expectation(mu_o, cov_o, self._obs_flat)
         g_lin = torch.zeros((B * T, d), dtype=torch.float64, device=self.device).index_add_(0, self.obs_node_ids, g1.reshape(-1, d))
         g_diag = torch.zeros((B * T, d, d), dtype=torch.float64, device=self.device).index_add_(0, self.obs_node_ids, g2.reshape(-1, d, d))
         u = tape.fisher_vector_product(pl, diag, sub, mu, cov, csub, g_lin.view(B, T, d), g_diag.view(B, T, d, d), torch.zeros_like(sub))
@@ -1197,7 +1218,6 @@ class CVISitesSDEQuadrature(CVISitesSSM):
         """(KL [B], (d/d eta_lin, d/d eta_diag, d/d eta_sub) packed) (variational_cvi_sde.py:488-493)."""
         pl = self.plan
         if self.native:
-            from . import quad
             kl, (g1, gd, gs) = quad.kl(self._quad_prm(), *self._marginals_natural(), grad=True)
             return kl, (pl.pack(VEC, g1), pl.pack(SYM, gd), pl.pack(FULL, gs))
         eta = [e.detach().requires_grad_(True) for e in self._expectations_natural()]
@@ -1215,9 +1235,7 @@ class CVISitesSDEQuadrature(CVISitesSSM):
         for qq, gg in ((tq.lin, g1), (tq.diag, gd), (tq.sub, gs)):
             pl.lincomb(qq, 1.0, qq, -float(lr), gg)
         pl.scatter_nodes_pair(tq.lin, tq.diag, self.obs_node_ids, self.data_nat1, self.data_nat2, scale=lr)
-        self._q = None
-        self._obs_fresh = False
-        self._started = True
+        self._sites_moved()
 
 
 def tranform_girsanov_sites(plan, girsanov_sites, current_prior_nat, new_prior_nat):
@@ -1239,7 +1257,6 @@ def _ssm_from_packed(plan, A, off, chol):
     ssm.batch_shape = (plan.B,)
     ssm.B, ssm.T, ssm.d = plan.B, T, d
     ssm.plan = plan
-    from .state_space_model import PackedSSM
     ssm._packed = PackedSSM(plan, A, off, chol)
     ssm._prec = None
     ssm._post = None

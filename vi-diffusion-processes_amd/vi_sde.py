@@ -17,6 +17,7 @@ import torch
 from . import _lib, linalg
 from ._lib import FULL, SYM, TRI, VEC
 from .packed import Plan, _ptr, _stream, aligned_segment_length, observation_period
+from .stamps import Stamp
 from .variational_cvi_sde import grid_indices
 
 
@@ -361,9 +362,9 @@ class VariationalMarkovGP:
         mu0, P0inv, ldP0 = self._prior_x0_device()
         # a function of q(x0) and p(x0) alone (~15 d x d launches): kept until either moves (update_initial_statistics assigns new tensors,
         # in-place edits move the version counters, the prior's initial state is compared by value)
-        key = (self.q0_mu, self.q0_mu._version, self.q0_chol, self.q0_chol._version, mu0, P0inv)
+        key = (self.q0_mu, self.q0_chol, mu0, P0inv)
         c = getattr(self, "_kl0", None)
-        if c is not None and len(c[0]) == len(key) and all(a is b if isinstance(a, torch.Tensor) else a == b for a, b in zip(c[0], key)):
+        if c is not None and c[0].matches(*key):
             return c[1]
         S0 = self.q0_chol @ self.q0_chol.transpose(-1, -2)
         dm = mu0 - self.q0_mu
@@ -371,7 +372,7 @@ class VariationalMarkovGP:
         mh = ((dm @ P0inv) * dm).sum(-1)
         ld0 = 2.0 * torch.log(torch.diagonal(self.q0_chol, dim1=-2, dim2=-1)).sum(-1)
         out = 0.5 * (tr + mh - d + ldP0 - ld0)
-        self._kl0 = (key, out)
+        self._kl0 = (Stamp(*key), out)
         return out
 
     def _prior_x0_device(self):
