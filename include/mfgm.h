@@ -1000,6 +1000,51 @@ int mfgm_readout_obs_ve(const mfgm_plan* plan, const mfgm_readout* readout, cons
                         const long long* node_ids, int n_per, const double* y, double* out_mu, double* out_cov, double* ve,
                         void* stream);
 
+/* ---- multi-latent sparse CVI (multi_latent_variational.py; markovflow/likelihoods/mutlistage_likelihood.py; csrc/mfgm_ml.h) --------------
+ * Sparse CVI on pairs of inducing states whose state stacks L independent latent processes (IndependentMultiOutput: state layout
+ * [latent l][component k], D = sum dl), under a likelihood that takes the factorised marginals q(F) = prod_l q(F_l) of the L latent
+ * values at a data point.  Latent l owns the slots off_l .. off_l + dl[l] (off_l = dl[0] + .. + dl[l-1]) of both halves of the pair; the
+ * projections of a point onto the L latents have disjoint supports, so one row h_i [2D] = sum_l (H P_i)[l, :] carries all of them.
+ * seg, the intervals and the prior padding are those of mfgm_sparse_data (one process: every interval).  Device pointers. */
+typedef struct mfgm_ml_data {
+    int M, L, N;              /* inducing states, latents (1..8), data points */
+    int dl[8];                /* state dimension of each latent, D = sum dl, 2 <= D <= 32 */
+    const int* seg;           /* [M + 2] CSR offsets per interval, as mfgm_sparse_data */
+    const double* h;          /* [N, 2D]: h[i, half*D + off_l + k], the dense-w layout */
+    const double* c;          /* [N, L] conditional variance of f_l(t_i) given the pair */
+    const double* prior_mean; /* [D] */
+    const double* prior_cov;  /* [D, D] */
+} mfgm_ml_data;
+typedef struct mfgm_ml_lik { int kind; double param[2]; } mfgm_ml_lik;
+#define MFGM_ML_NONE 0        /* prediction only */
+#define MFGM_ML_MULTISTAGE 1  /* L == 3, param = (jitter in [0, 1/2), bin size > 0) */
+#define MFGM_ML_HETGAUSS 2    /* L == 2 */
+/* Per point i of interval m and latent l, with pmu_m / PC_m the mean / covariance of the pair of interval m assembled from mu [M, D],
+ * Sig, Sub [M, D, D] as mfgm_sparse_predict assembles them (only the within-latent blocks of PC_m are read):
+ *     fmu[i, l] = sum_r h_ir pmu_m[r],   fvar[i, l] = c[i, l] + sum_{r, c'} h_ir PC_m[r][c'] h_ic'     over the 2 dl[l] slots of latent l,
+ * and, in the same launch and from those very values, the likelihood's VE_i and its gradients with respect to the expectation
+ * parameters of every latent,  g1[i, l] = dVE/dm_l - 2 (dVE/dv_l) m_l,  g2[i, l] = dVE/dv_l:
+ *   MFGM_ML_MULTISTAGE  y == 0: B+(F0);  y == 1: B-(F0) + B+(F1);  y >= 2: B-(F0) + B-(F1) + Pois(y - 2; F2);  any other y (negative,
+ *       NaN, non-integer below 2): VE = 0 and zero gradients.  B+- = the MFGM_LIK_BERNOULLI rule of mfgm_scalar_lik with label 1 / 0,
+ *       Pois = its MFGM_LIK_POISSON closed form; a latent outside the point's case has zero gradients.
+ *   MFGM_ML_HETGAUSS    y ~ N(F0, exp F1):  VE = -1/2 [log 2 pi + m1 + exp(-m1 + v1 / 2) ((m0 - y)^2 + v0)].
+ * fvar <= 0 is not clamped.  fmu, fvar, g1, g2 [N, L]; ve_part [M + 1] = the interval's sum of VE_i in a fixed order (0 for an empty
+ * interval); any of the five outputs may be NULL and is then not written.  With MFGM_ML_NONE y, ve_part, g1, g2 must be NULL. */
+int mfgm_ml_predict_lik(const mfgm_ml_data* data, const mfgm_ml_lik* lik, const double* y, const double* mu, const double* Sig,
+                        const double* Sub, double* fmu, double* fvar, double* ve_part, double* g1, double* g2, void* stream);
+/* In place, for nat1 [M + 1, 2D] and nat2 [M + 1, 2D, 2D] (dense, both triangles written) or the quadrant-packed
+ * nat2q [M + 1, D (D + 1) + D^2] of mfgm_sparse_factor_q:
+ *     nat1[m][r]    <- (1 - lr) old + lr sum_i g1[i, l(r)] h_ir
+ *     nat2[m][r][c] <- (1 - lr) old + lr sum_i g2[i, l] h_ir h_ic     r, c slots of the same latent l, in either half
+ *     nat2[m][r][c] <- (1 - lr) old  exactly                          r, c slots of different latents.
+ * One owner per entry, no atomics; N = 0 decays the sites.
+ * All three entry points: fp64, no allocation, no host synchronisation (graph-capturable), two launches on the same inputs agree bit
+ * for bit; they return 1 before any launch for L outside 1 .. 8, a dl < 1, D outside 2 .. 32, a kind whose L does not fit, a parameter
+ * out of range, lr outside [0, 1], or a missing pointer when N > 0. */
+int mfgm_ml_site_update(const mfgm_ml_data* data, const double* g1, const double* g2, double lr, double* nat1, double* nat2, void* stream);
+int mfgm_ml_site_update_q(const mfgm_ml_data* data, const double* g1, const double* g2, double lr, double* nat1, double* nat2q,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,4 +14,7 @@ def __getattr__(name):
     if name == "SpatioTemporalSparseCVI":
         from .spatio_temporal_variational import SpatioTemporalSparseCVI
         return SpatioTemporalSparseCVI
+    if name == "MultiLatentSparseCVI":
+        from .multi_latent_variational import MultiLatentSparseCVI
+        return MultiLatentSparseCVI
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -162,6 +162,9 @@ EXPORTS = {
     "mfgm_readout_site_update": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5
                                  + [ctypes.c_double, ctypes.c_void_p]),
     "mfgm_readout_obs_ve": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] + [ctypes.c_void_p] * 5),
+    "mfgm_ml_predict_lik": (ctypes.c_int, [ctypes.c_void_p] * 12),
+    "mfgm_ml_site_update": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
+    "mfgm_ml_site_update_q": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
 }
 
 
@@ -203,6 +206,20 @@ class StData(ctypes.Structure):
     _fields_ = [("M", ctypes.c_int), ("Ms", ctypes.c_int), ("dt", ctypes.c_int), ("N", ctypes.c_int), ("seg", ctypes.c_void_p),
                 ("a", ctypes.c_void_p), ("h", ctypes.c_void_p), ("c", ctypes.c_void_p), ("prior_mean", ctypes.c_void_p),
                 ("prior_cov", ctypes.c_void_p)]
+
+
+class MlData(ctypes.Structure):
+    """mfgm_ml_data (include/mfgm.h)."""
+    _fields_ = [("M", ctypes.c_int), ("L", ctypes.c_int), ("N", ctypes.c_int), ("dl", ctypes.c_int * 8), ("seg", ctypes.c_void_p),
+                ("h", ctypes.c_void_p), ("c", ctypes.c_void_p), ("prior_mean", ctypes.c_void_p), ("prior_cov", ctypes.c_void_p)]
+
+
+class MlLik(ctypes.Structure):
+    """mfgm_ml_lik (include/mfgm.h)."""
+    _fields_ = [("kind", ctypes.c_int), ("param", ctypes.c_double * 2)]
+
+
+ML_NONE, ML_MULTISTAGE, ML_HETGAUSS = 0, 1, 2
 
 
 class KfSites(ctypes.Structure):

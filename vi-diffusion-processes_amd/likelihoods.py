@@ -10,6 +10,9 @@ Gauss-Hermite variational expectations and their site gradients, natively in one
 
 LinearReadout, last, lets the diffusion models see their state through f = H x + c with one of these scalar likelihoods per output
 (DESIGN.md section 19).
+
+MultiStageLikelihood and HeteroskedasticGaussian, at the end, couple several latent GPs at one observation: the likelihoods of
+MultiLatentSparseCVI.
 """
 import math
 
@@ -567,3 +570,150 @@ class LinearReadout:
 
         lp = self._per_output(one, m, v, y)
         return torch.where(seen, lp, torch.zeros_like(lp)).sum(-1)
+
+
+# ---- multi-latent likelihoods (markovflow/likelihoods/mutlistage_likelihood.py; docs/notebooks/stacked_kernels.py) -------------------------
+class _MultiLatentLikelihood:
+    """A likelihood of one observation y that couples `latent_dim` latent values through the factorised marginals
+    q(F) = prod_l N(F_l; Fmu_l, Fvar_l).  Fmu, Fvar [..., L], Y [..., 1]; variational_expectations [...]; the gradients with respect to
+    the expectation parameters of every latent, g1_l = dVE/dm_l - 2 (dVE/dv_l) m_l and g2_l = dVE/dv_l, [..., L] each, in explicit
+    form (for a quadrature term: the derivatives of the rule, as mfgm_scalar_lik defines them).  Plain torch on any device: the torch
+    route of MultiLatentSparseCVI and the anchor of its kernels (include/mfgm.h, mfgm_ml_predict_lik)."""
+
+    latent_dim = None
+    ml_kind = None          # mfgm_ml_lik kind of the native route
+
+    @property
+    def ml_params(self):
+        return (0.0, 0.0)
+
+    def _ve_and_derivatives(self, Fmu, Fvar, Y):
+        """(VE [...], dVE/dm [..., L], dVE/dv [..., L])."""
+        raise NotImplementedError
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        return self._ve_and_derivatives(Fmu, Fvar, Y)[0]
+
+    def ve_gradients_expectation(self, Fmu, Fvar, Y):
+        _, dm, dv = self._ve_and_derivatives(Fmu.detach(), Fvar.detach(), Y.detach())
+        return dm - 2.0 * dv * Fmu.detach(), dv
+
+    def predict_log_density(self, Fmu, Fvar, Y):
+        raise NotImplementedError(f"{type(self).__name__} has no predictive density (as in the reference)")
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        raise NotImplementedError(f"{type(self).__name__} has no predictive moments (as in the reference)")
+
+
+class MultiStageLikelihood(_MultiLatentLikelihood):
+    """markovflow/likelihoods/mutlistage_likelihood.py: intermittent-demand counts through a decision tree of three latents,
+        y == 0:  log p = B+(F0);     y == 1:  log p = B-(F0) + B+(F1);     y >= 2:  log p = B-(F0) + B-(F1) + Pois(y - 2; F2)
+    with B+- the jittered-probit Bernoulli log-probability of label 1 / 0 (Bernoulli above) and Pois the exp-link Poisson with bin size
+    `binsize` (Poisson above).  Any other y (negative, NaN, non-integer below 2) contributes zero to everything, as the reference's
+    where-chain.  The variational expectation applies the same cases to the per-latent expectations: the 20-point Gauss-Hermite rule
+    for the Bernoulli terms, the closed form for the Poisson term; a latent outside a point's case has zero gradients there."""
+
+    latent_dim = 3
+    ml_kind = _lib.ML_MULTISTAGE
+
+    def __init__(self, jitter=1e-3, binsize=1.0):
+        import numpy as np
+        self.jitter, self.binsize = float(jitter), float(binsize)
+        if not 0.0 <= self.jitter < 0.5:
+            raise ValueError("jitter must lie in [0, 1/2)")
+        if not (self.binsize > 0.0 and math.isfinite(self.binsize)):
+            raise ValueError("binsize must be positive")
+        xi, w = np.polynomial.hermite.hermgauss(20)
+        self._xi, self._w = xi, w / math.sqrt(math.pi)
+        self._rule_cache = {}
+
+    @property
+    def ml_params(self):
+        return (self.jitter, self.binsize)
+
+    def _rule(self, like):
+        key = str(like.device)
+        r = self._rule_cache.get(key)
+        if r is None:
+            r = self._rule_cache[key] = (torch.tensor(self._xi, dtype=torch.float64, device=like.device),
+                                         torch.tensor(self._w, dtype=torch.float64, device=like.device))
+        return r
+
+    def _p(self, f):
+        return self.jitter + (1.0 - 2.0 * self.jitter) * _probit(f)
+
+    def _bernoulli_rule(self, mu, v, s):
+        """(VE, dVE/dmu, dVE/dv) of log p_j(s F) under N(mu, v) by the 20-point rule; s = +1 for label 1, -1 for label 0."""
+        xi, w = self._rule(mu)
+        sc = math.sqrt(2.0) * torch.sqrt(v)
+        X = mu[..., None] + sc[..., None] * xi
+        p = self._p(s[..., None] * X)
+        dl = s[..., None] * (1.0 - 2.0 * self.jitter) * torch.exp(-0.5 * X * X) * (1.0 / math.sqrt(2.0 * math.pi)) / p
+        return (w * torch.log(p)).sum(-1), (w * dl).sum(-1), (w * dl * xi).sum(-1) / sc
+
+    @staticmethod
+    def _cases(Y):
+        y = Y[..., 0]
+        return y == 0, y == 1, y >= 2
+
+    def _ve_and_derivatives(self, Fmu, Fvar, Y):
+        is0, is1, big = self._cases(Y)
+        one = torch.ones_like(Fmu[..., 0])
+        zero = torch.zeros_like(one)
+        ve0, a0, e0 = self._bernoulli_rule(Fmu[..., 0], Fvar[..., 0], torch.where(is0, one, -one))
+        ve1, a1, e1 = self._bernoulli_rule(Fmu[..., 1], Fvar[..., 1], torch.where(is1, one, -one))
+        cnt = torch.where(big, Y[..., 0] - 2.0, zero)
+        rate = self.binsize * torch.exp(Fmu[..., 2] + 0.5 * Fvar[..., 2])
+        ve2 = cnt * math.log(self.binsize) + cnt * Fmu[..., 2] - rate - torch.lgamma(cnt + 1.0)
+        in0, in1 = is0 | is1 | big, is1 | big
+        ve = torch.where(in0, ve0, zero) + torch.where(in1, ve1, zero) + torch.where(big, ve2, zero)
+        dm = torch.stack([torch.where(in0, a0, zero), torch.where(in1, a1, zero), torch.where(big, cnt - rate, zero)], -1)
+        dv = torch.stack([torch.where(in0, e0, zero), torch.where(in1, e1, zero), torch.where(big, -0.5 * rate, zero)], -1)
+        return ve, dm, dv
+
+    def log_prob(self, F, Y):
+        """log p(y | F), [...]."""
+        is0, is1, big = self._cases(Y)
+        zero = torch.zeros_like(F[..., 0])
+        cnt = torch.where(big, Y[..., 0] - 2.0, zero)
+        lp0, ln0 = torch.log(self._p(F[..., 0])), torch.log(self._p(-F[..., 0]))
+        lp1, ln1 = torch.log(self._p(F[..., 1])), torch.log(self._p(-F[..., 1]))
+        lp2 = cnt * (math.log(self.binsize) + F[..., 2]) - self.binsize * torch.exp(F[..., 2]) - torch.lgamma(cnt + 1.0)
+        return torch.where(is0, lp0, zero) + torch.where(is1, ln0 + lp1, zero) + torch.where(big, ln0 + ln1 + lp2, zero)
+
+    def sample_y(self, F, seed=0):
+        """y [..., 1] drawn from p(y | F) down the tree: y = 0 with probability p_j(F0), else 1 with probability p_j(F1), else
+        2 + Poisson(binsize e^{F2}) (sample_y of the reference, on a torch generator seeded with `seed`)."""
+        gen = torch.Generator(device=F.device)
+        gen.manual_seed(int(seed))
+        eta0 = torch.bernoulli(self._p(F[..., 0]), generator=gen)
+        eta1 = torch.bernoulli(self._p(F[..., 1]), generator=gen)
+        lam = torch.poisson(self.binsize * torch.exp(F[..., 2]), generator=gen)
+        y = torch.where((eta0 == 0) & (eta1 == 1), torch.ones_like(lam), torch.zeros_like(lam))
+        return (y + torch.where((eta0 == 0) & (eta1 == 0), lam + 2.0, torch.zeros_like(lam)))[..., None]
+
+
+class HeteroskedasticGaussian(_MultiLatentLikelihood):
+    """y ~ N(F0, exp F1): one latent for the mean and one for the log-variance (docs/notebooks/stacked_kernels.py of the reference).
+    VE = -1/2 [log 2 pi + m1 + exp(-m1 + v1 / 2) ((m0 - y)^2 + v0)] in closed form; dVE/dv_l <= 0 for both latents at every input, so
+    the posterior precision stays positive definite."""
+
+    latent_dim = 2
+    ml_kind = _lib.ML_HETGAUSS
+
+    def _ve_and_derivatives(self, Fmu, Fvar, Y):
+        m0, m1, v0, v1 = Fmu[..., 0], Fmu[..., 1], Fvar[..., 0], Fvar[..., 1]
+        s = torch.exp(-m1 + 0.5 * v1)
+        r = m0 - Y[..., 0]
+        q = r * r + v0
+        ve = -0.5 * (math.log(2.0 * math.pi) + m1 + s * q)
+        return ve, torch.stack([-s * r, -0.5 + 0.5 * s * q], -1), torch.stack([-0.5 * s, -0.25 * s * q], -1)
+
+    def log_prob(self, F, Y):
+        return -0.5 * (math.log(2.0 * math.pi) + F[..., 1] + torch.exp(-F[..., 1]) * (Y[..., 0] - F[..., 0]) ** 2)
+
+    def sample_y(self, F, seed=0):
+        gen = torch.Generator(device=F.device)
+        gen.manual_seed(int(seed))
+        eps = torch.randn(F.shape[:-1], dtype=F.dtype, device=F.device, generator=gen)
+        return (F[..., 0] + torch.exp(0.5 * F[..., 1]) * eps)[..., None]
