@@ -568,6 +568,25 @@ int mfgm_packed_kernel_ssm(const mfgm_plan* plan, const mfgm_kernel_terms* terms
 int mfgm_packed_kernel_score(const mfgm_plan* plan, const mfgm_kernel_terms* terms, const double* time_deltas, const double* x,
                              const double* Sig, const double* Sub, double* score, void* ws, int* info, void* stream);
 
+/* Score of the sparse-CVI bound (sparse_variational_cvi.py:270-292) with respect to the kernel terms' parameters THROUGH THE
+ * CONDITIONALS p(f(t_i) | s(z-), s(z+)) of the data points, at a fixed posterior q of the inducing states:
+ *   sum_i a_i d fmu_i + b_i d fvar_i,   fmu_i = w_i . mu_pair,   fvar_i = c_i + w_i^T Sigma_pair w_i,
+ * where (w_i, c_i) are functions of the kernel and of the gaps gap_lo[i] = t_i - z-, gap_hi[i] = z+ - t_i around the point (the
+ * caller pads the two ends, conditionals.py:207-256).  Per term, in covariance form (a point may sit on an inducing point):
+ *   Q_mp = Q2 + A2 Q1 A2^T,  x = Q_mp^-1 A2 Q1 h,  y = h - A2^T x,  w+ = x,  w- = A1^T y,  c = h^T Q1 y,
+ * with (A, Q) those of mfgm_packed_kernel_ssm rebuilt from the same closed forms, differentiated in reverse mode (csrc/
+ * mfgm_sparse_score.h); the prior padding of the intervals 0 and M adds b w^T dPinf w.  data: every interval (m_hi <= 0), d <= 8;
+ * w is read, c is not; a, b [N]: d ve_i / d fmu_i and d ve_i / d fvar_i; mu, Sig, Sub as mfgm_sparse_predict takes them.
+ * score: natural [8, 3, 2] in the layout of mfgm_packed_kernel_score (the CALLER's factor order).  An exactly-zero Q_mp block
+ * contributes through w- = A1^T h alone; *info is set when a Q_mp block is neither positive definite nor zero.
+ * ws: mfgm_sparse_cond_score_workspace_doubles(N) doubles (one partial per wavefront and plane, summed in a fixed order: no
+ * floating-point atomics, two calls give identical bits).  Returns 1, before any HIP call, for a null argument, d > 8, a sharded
+ * data (m_hi > 0) and whatever terms mfgm_packed_kernel_ssm rejects. */
+size_t mfgm_sparse_cond_score_workspace_doubles(int N);
+int mfgm_sparse_cond_score(const mfgm_sparse_data* data, const mfgm_kernel_terms* terms, const double* gap_lo, const double* gap_hi,
+                           const double* a, const double* b, const double* mu, const double* Sig, const double* Sub, double* score,
+                           void* ws, int* info, void* stream);
+
 /* A piecewise-stationary kernel (kernels/piecewise_stationary.py `PiecewiseKernel`): nregion - 1 change points c_k cut the time axis
  * into nregion regions, region r(t) = #{c_k <= t} (a point on a change point belongs to the region after it).  All regions share
  * base's structure (nterm, nfactor, offset, kind) and jitter; region r has the rates rate[r], variances var[r] (both indexed as

@@ -21,6 +21,11 @@ Two routes:
   fallback  any other kernel with `_parts(dt, leaves)` (state_dim > 8, LatentExponentiallyGenerated): the cotangents as batched torch
             expressions on the unpacked moments (vidp_amd.linalg for the d x d solves), then one backward pass through `_parts`.
 VIDP_NATIVE_SCORE=0 forces the fallback.
+
+The sparse CVI model (SparseCVIGaussianProcess.elbo_and_grad) differentiates its ELBO at fixed sites with the
+same two routes for the chain part, fed with the moments displaced by a Fisher-vector product, plus a part through the conditionals
+of the data points: one launch of mfgm_sparse_cond_score (csrc/mfgm_sparse_score.h) natively, autograd through `_parts` otherwise
+(`sparse_elbo_grad`; VIDP_NATIVE_SPARSE_SCORE=0 forces the torch route).
 """
 import math
 import os
@@ -174,6 +179,190 @@ def kernel_score(kernel, kalman, time_points):
     dts = (t[:, 1:] - t[:, :-1]).contiguous() if plan.T > 1 else None
     grads = (score_native if native else score_fallback)(kernel, plan, dts, moments)
     return ll, grads, moments, disp
+
+
+# -- the sparse CVI bound at fixed sites ----------------------------------------------------------------------------
+def _add_grads(like, *parts):
+    """Sum of gradient structures of the shape of `like`."""
+    flats = [flatten(p) for p in parts]
+    return unflatten(like, [sum(g[1:], g[0]) for g in zip(*flats)])
+
+
+def overlap_add(n1, n2):
+    """Pair sites (n1 [M + 1, 2d], n2 [M + 1, 2d, 2d]) -> the chain's (lin [M, d], diag [M, d, d], sub [M - 1, d, d]) in
+    mfgm_sparse_theta's convention: site t + 1 starts at inducing state t, site t ends there; sub takes twice the lower-left block."""
+    d = n1.shape[-1] // 2
+    lin = n1[1:, :d] + n1[:-1, d:]
+    diag = n2[1:, :d, :d] + n2[:-1, d:, d:]
+    sub = 2.0 * n2[1:-1, d:, :d]
+    return lin, diag, sub
+
+
+def sparse_conditional_inputs(time_points, inducing):
+    """(interval index, t - z-, z+ - t) of sorted data points among the inducing points, the ends padded as the conditionals pad them."""
+    from .conditionals import APPROX_INF
+    idx = torch.searchsorted(inducing.contiguous(), time_points.contiguous())
+    inf = APPROX_INF * torch.ones_like(inducing[-1:])
+    aug = torch.cat([-inf, inducing, inf])
+    return idx, (time_points - aug[idx]).contiguous(), (aug[idx + 1] - time_points).contiguous()
+
+
+def conditional_part_torch(kernel, gap_lo, gap_hi, a, b, mu_pair, Sig_pair, idx, M):
+    """Gradients of  sum_i a_i fmu_i + b_i fvar_i  at fixed pair moments through the conditionals, by autograd through kernel._parts:
+    Q_mp = Q2 + A2 Q1 A2^T, x = Q_mp^-1 A2 Q1 h, y = h - A2^T x, w = (A1^T y, x), c = h^T Q1 y.  mu_pair [N, 2d], Sig_pair [N, 2d, 2d]:
+    the pair marginals of the points' intervals, whose prior padding at the two ends is replaced by Pinf(leaves) + jitter I here."""
+    from . import tape
+    dev = gap_lo.device
+    d = kernel.state_dim
+    leaves = kernel.hyperparameter_leaves(dev)
+    eye = torch.eye(d, dtype=torch.float64, device=dev)
+    A1, P, Q1, _ = kernel._parts(gap_lo, leaves)
+    A2, _, Q2, _ = kernel._parts(gap_hi, leaves)
+    Q1, Q2 = Q1 + kernel.jitter * eye, Q2 + kernel.jitter * eye
+    h = kernel._emission_row().to(dev)[:, None]
+    u = Q1 @ h
+    Qmp = Q2 + A2 @ Q1 @ A2.transpose(-1, -2)
+    x = tape.cholesky_solve(tape.cholesky(0.5 * (Qmp + Qmp.transpose(-1, -2))), A2 @ u)
+    y = h - A2.transpose(-1, -2) @ x
+    w = torch.cat([A1.transpose(-1, -2) @ y, x], dim=-2)[..., 0]
+    c = (u * y).sum(dim=(-1, -2))
+    P0 = P + kernel.jitter * eye
+    lo, hi = (idx == 0)[:, None, None], (idx == M)[:, None, None]
+    S = Sig_pair.clone()
+    S[:, :d, :d] = torch.where(lo, P0, S[:, :d, :d])
+    S[:, d:, d:] = torch.where(hi, P0, S[:, d:, d:])
+    fmu = (w * mu_pair).sum(-1)
+    fvar = c + (w[:, None, :] @ S @ w[:, :, None])[:, 0, 0]
+    return _grads_of(leaves, (a * fmu).sum() + (b * fvar).sum())
+
+
+def conditional_part_native(kernel, plan, data, gap_lo, gap_hi, a, b, marg):
+    """The same gradients from one launch of mfgm_sparse_cond_score on the fused route's data (csrc/mfgm_sparse_score.h)."""
+    import ctypes
+    from .kernels import _NOT_PD
+    from .packed import _ptr, _stream
+    lib = plan.lib
+    ws = data.get("score_ws")
+    if ws is None:
+        ws = data["score_ws"] = torch.empty(int(lib.mfgm_sparse_cond_score_workspace_doubles(data["N"])), dtype=torch.float64, device=a.device)
+    terms = kernel._terms()
+    score = torch.empty((8, 3, 2), dtype=torch.float64, device=a.device)
+    # the entry point takes whole chains only and says so by m_hi <= 0; the model's struct names its range (0, M + 1) explicitly
+    sd, src = _lib.SparseData(), data["struct"]
+    for name, _ in _lib.SparseData._fields_:
+        setattr(sd, name, getattr(src, name))
+    sd.m_lo, sd.m_hi = 0, 0
+    _lib.check(lib.mfgm_sparse_cond_score(ctypes.byref(sd), ctypes.byref(kernel._terms_struct(terms)), _ptr(gap_lo), _ptr(gap_hi),
+                                          _ptr(a), _ptr(b), _ptr(marg["mu"]), _ptr(marg["Sig"]), _ptr(marg["Sub"]), _ptr(score), _ptr(ws),
+                                          _ptr(plan.info), _stream()), "mfgm_sparse_cond_score")
+    try:
+        plan.check_info()
+    except ArithmeticError as e:
+        raise ArithmeticError(_NOT_PD) from e
+    g = score.cpu()
+    leaves = kernel.hyperparameter_leaves("cpu")
+    objective = torch.zeros((), dtype=torch.float64)
+    for c, factors in enumerate(kernel._terms_t(leaves)):
+        for f, (_, rate, var) in enumerate(factors):
+            objective = objective + rate * g[c, f, 0] + var * g[c, f, 1]
+    return _grads_of(leaves, objective)
+
+
+def sparse_native_route(model, data):
+    """Whether elbo_and_grad takes the HIP route: the fused data route applies and the chain part's score is native."""
+    return (data is not None and os.environ.get("VIDP_NATIVE_SPARSE_SCORE", "1") != "0"
+            and native_route(model._kernel, model.dist_p.plan))
+
+
+def sparse_elbo_grad(model, input_data, parts=None):
+    """Exact gradient of SparseCVIGaussianProcess.classic_elbo with respect to the kernel's hyper-parameters at fixed sites (structure of
+    hyperparameter_leaves(), CPU fp64).  With theta_p the prior's naturals on the inducing chain, theta_s the overlap-added sites, F the
+    Fisher matrix of q and g^ the overlap-added CVI target sum_i (g1_i w_i, g2_i w_i w_i^T),
+        dL = < eta_q - eta_p + F (g^ - theta_s), d theta_p >  +  sum_i a_i d fmu_i + b_i d fvar_i  (q fixed),
+    a = g1 + 2 g2 fmu, b = g2.  The first bracket is the log-likelihood score on moments displaced by the Fisher-vector product (its
+    linear component meets d theta_p's, which is zero for a zero-mean prior); the second goes through the conditionals.
+    parts (a dict): receives the two chain contributions and the conditional one separately."""
+    from . import tape
+    kernel, lik = model._kernel, model._likelihood
+    time_points, observations = input_data
+    z = model.inducing_inputs
+    data = model._data(input_data)
+    native = sparse_native_route(model, data)
+    p = model.dist_p
+    pl, T, d = p.plan, p.T, p.d
+    m = model._marginals()
+    if data is not None:
+        fmu, fvar = model._predict_f_data(data)
+        y = model._own_observations(data, observations)
+    else:
+        fmu, fvar = model.posterior.predict_f(time_points)
+        y = observations
+    g1, g2 = lik.ve_gradients_expectation(fmu, fvar, y)
+    g1, g2, fm = g1.reshape(-1).detach(), g2.reshape(-1).detach(), fmu.reshape(-1).detach()
+    a, b = (g1 + 2.0 * g2 * fm).contiguous(), g2.contiguous()
+    c = data.get("gaps") if data is not None else None
+    if c is None:
+        c = sparse_conditional_inputs(time_points.reshape(-1), z)
+        if data is not None:
+            data["gaps"] = c
+    idx, gap_lo, gap_hi = c
+    # ---- the CVI target g^ (what update_sites accumulates at lr = 1 into zero sites) minus the sites, on the chain
+    if native:
+        import ctypes
+        from .packed import _ptr, _stream
+        t1, t2 = torch.zeros_like(model.nat1), torch.zeros_like(model.nat2)
+        _lib.check(pl.lib.mfgm_sparse_site_update(ctypes.byref(data["struct"]), _ptr(g1.contiguous()), _ptr(g2.contiguous()), 1.0, _ptr(t1),
+                                                  _ptr(t2), _stream()), "mfgm_sparse_site_update")
+    else:
+        wfull = data["keep"][1][:data["N"]] if data is not None else None
+        if wfull is None:
+            from .conditionals import conditional_statistics
+            H = kernel.generate_emission_model(time_points).emission_matrix
+            Pc, _ = conditional_statistics(time_points, z, kernel)
+            wfull = (H @ Pc)[:, 0, :]
+        t1 = torch.zeros_like(model.nat1).index_add_(0, idx, g1[:, None] * wfull)
+        t2 = torch.zeros_like(model.nat2).index_add_(0, idx, g2[:, None, None] * wfull[:, :, None] * wfull[:, None, :])
+    v_lin, v_diag, v_sub = overlap_add(t1 - model.nat1, t2 - model.nat2)
+    # ---- chain part: the score on (mu, Sig + delta_diag, Sub + delta_sub), delta = F (g^ - theta_s)
+    model._theta()
+    tb = model._theta_bufs
+    mu, cov, csub = m["mu"][None], m["Sig"][None], m["Sub"][None, :T - 1]
+    _, dd, ds = tape.fisher_vector_product(pl, tb["diag"][None], tb["sub"][None, :T - 1], mu, cov, csub, v_lin[None], v_diag[None], v_sub[None])
+    s = m["packed"]
+    dts = (z[1:] - z[:-1]).reshape(1, -1).contiguous() if T > 1 else None
+    score = score_native if native else score_fallback
+
+    def packed_band(diag, sub):
+        return pl.pack(SYM, diag.contiguous()), (pl.pack(FULL, sub.contiguous()) if T > 1 else pl.zeros(FULL))
+
+    if parts is None:
+        pd, ps = packed_band(cov + dd, csub + ds)
+        chain = score(kernel, pl, dts, dict(x=s["x"], Sig=pd, Sub=ps))
+    else:
+        # the two brackets apart: the score is affine in the second moments, so F's share is a difference of two scores
+        parts["chain_kl"] = score(kernel, pl, dts, dict(x=s["x"], Sig=s["Sig"], Sub=s["Sub"]))
+        pd, ps = packed_band(cov + dd, csub + ds)
+        both = score(kernel, pl, dts, dict(x=s["x"], Sig=pd, Sub=ps))
+        parts["chain_fisher"] = _add_grads(both, both, unflatten(both, [-g for g in flatten(parts["chain_kl"])]))
+        chain = both
+    # ---- conditional part
+    if native:
+        cond = conditional_part_native(kernel, pl, data, gap_lo, gap_hi, a, b, m)
+    else:
+        mean = kernel.initial_mean(()).to(z.device, torch.float64)
+        cov0 = kernel.initial_covariance(z[:1]).to(z.device, torch.float64)
+        ext_m = torch.cat([mean[None], m["mu"], mean[None]])
+        ext_c = torch.cat([cov0[None], m["Sig"], cov0[None]])
+        zero = torch.zeros_like(cov0)[None]
+        ext_s = torch.cat([zero, m["Sub"][:T - 1], zero])                   # Cov(x_hi, x_lo) of interval k
+        mu_pair = torch.cat([ext_m[:-1], ext_m[1:]], dim=-1)[idx]
+        top = torch.cat([ext_c[:-1], ext_s.transpose(-1, -2)], dim=-1)
+        bot = torch.cat([ext_s, ext_c[1:]], dim=-1)
+        Sig_pair = torch.cat([top, bot], dim=-2)[idx]
+        cond = conditional_part_torch(kernel, gap_lo, gap_hi, a, b, mu_pair, Sig_pair, idx, T)
+    if parts is not None:
+        parts["conditional"] = cond
+    return _add_grads(chain, chain, cond)
 
 
 # -- unconstrained parametrisations of the positive scalars (KernelHyperTrainer) ---------------------------------------------------------

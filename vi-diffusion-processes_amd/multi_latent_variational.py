@@ -273,6 +273,10 @@ class MultiLatentSparseCVI(SparseCVIGaussianProcess):
         """(sum of variational expectations, (g1, g2) [N, L] with respect to the expectation parameters of every latent)."""
         return (self._likelihood.variational_expectations(Fmu, Fvar, Y).sum(), self._likelihood.ve_gradients_expectation(Fmu, Fvar, Y))
 
+    def elbo_and_grad(self, input_data):
+        raise NotImplementedError("elbo_and_grad is not implemented for MultiLatentSparseCVI: IndependentMultiOutput is outside the "
+                                  "kernel score (DESIGN.md section 21)")
+
     def classic_elbo(self, input_data):
         """sum_i E_q log p(y_i | F_i) - KL[q(s_Z) || p(s_Z)]."""
         data = self._data(input_data)

@@ -365,6 +365,10 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
         quad = (m["mu"] * (pn["lin"] + self._nat1[1:, :d] + self._nat1[:-1, d:])).sum()
         return 0.5 * float(p.T * d) * math.log(2.0 * math.pi) - m["logdetL"].reshape(()) + 0.5 * quad
 
+    def elbo_and_grad(self, input_data):
+        raise NotImplementedError("elbo_and_grad is not implemented for SparsePowerExpectationPropagation: its objective is the "
+                                  "energy, not the ELBO that SparseCVIGaussianProcess.elbo_and_grad differentiates")
+
     def energy(self, input_data):
         """The PEP energy  dist_q.normalizer() - dist_p.normalizer() + 1/alpha sum_m sum_{i in m} e_i  (sparse_pep.py:489-495, e_i at the
         cavity); a scalar tensor.  At the fixed point of a Gaussian likelihood with at most one point per interval it is

@@ -470,6 +470,31 @@ class SparseCVIGaussianProcess:
     def loss(self, input_data):
         return -self.classic_elbo(input_data)
 
+    # ---- kernel hyper-parameters ------------------------------------------------------------------------------------
+    def elbo_and_grad(self, input_data):
+        """(classic_elbo(input_data), its exact gradient with respect to the kernel's hyper-parameters with the sites held fixed): the
+        gradient in the structure of kernel.hyperparameter_leaves(), CPU fp64 tensors, as log_likelihood_and_grad() of the dense
+        models.  What the reference's sparse notebooks get from a GradientTape over `model.loss` between two site steps.  One chain,
+        every process its own: `shard=` is not covered."""
+        from . import hyper
+        hyper.precheck(self._kernel)
+        if self._shard is not None:
+            raise NotImplementedError("elbo_and_grad is not implemented for a chain shared between processes (shard=)")
+        if self.inducing_inputs.dim() != 1:
+            raise NotImplementedError("elbo_and_grad takes one chain of inducing points")
+        elbo = self.classic_elbo(input_data)
+        return elbo, hyper.sparse_elbo_grad(self, input_data)
+
+    def kernel_changed(self):
+        """The kernel's hyper-parameters were assigned: drop everything derived from them (the prior and its naturals, the data cache
+        with w and c, the marginal, prediction and KL caches, the theta and sweep buffers).  The sites stay."""
+        self._dist_p = None
+        self._pn, self._pmu = None, None
+        self._data_cache = None
+        self._marg, self._pred_cache, self._kl_cache = None, None, None
+        self.__dict__.pop("_theta_bufs", None)
+        self.__dict__.pop("_sweep_bufs", None)
+
     def predict_log_density(self, input_data, full_output_cov=False):
         """log p(y* | data) per point (markovflow/models/models.py:206-227): the likelihood's predict_log_density of posterior.predict_f."""
         X, Y = input_data

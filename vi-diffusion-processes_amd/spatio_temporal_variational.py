@@ -323,6 +323,10 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
         tr, mh = p.plan.kl_terms(s["Sig"], s["Sub"], s["x"], pn["nat"]["diag"], pn["nat"]["sub"], self._prior_mean_packed(), aD=-2.0, aS=-1.0)
         return (0.5 * (tr + mh - float(p.T * p.d) + 2.0 * pn["nat"]["sumlogchol"] + 2.0 * m["logdetL"])).sum()
 
+    def elbo_and_grad(self, input_data):
+        raise NotImplementedError("elbo_and_grad is not implemented for SpatioTemporalSparseCVI: the spatial kernel and the Kronecker "
+                                  "state are outside the kernel score (DESIGN.md section 21)")
+
     def classic_elbo(self, input_data):
         """sum_i E_q log p(y_i | f_i) - KL[q(s(Z_t)) || p(s(Z_t))] (:209-236)."""
         if self._data(input_data) is not None:

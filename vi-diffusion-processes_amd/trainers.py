@@ -472,7 +472,9 @@ class KernelHyperTrainer:
     """Learn a GP model's kernel hyper-parameters by Adam on its negative log marginal likelihood -- what the reference's GPR scripts
     and notebooks do with `Adam.minimize(model.loss, model.trainable_variables)` -- for GaussianProcessRegression and the sites models
     (CVIGaussianProcess, PowerExpectationPropagation).  The gradient is the model's log_likelihood_and_grad() (one factorisation, one
-    selected inverse, one score pass: hyper.py).
+    selected inverse, one score pass: hyper.py).  A model with elbo_and_grad(input_data)
+    (SparseCVIGaussianProcess) is trained on its negative ELBO at fixed sites instead and needs `input_data`,
+    which step() hands to elbo_and_grad and fit() to update_sites.
 
     Adam (tf defaults, `_Adam`) runs on unconstrained values: softplus^-1 of the positive scalars (gpflow's default `positive()`;
     transform="log" is the other choice), the identity for the LEG kernel's N and R.  learn_noise=True (GPR with a scalar
@@ -480,11 +482,17 @@ class KernelHyperTrainer:
 
     Single process only: the gradients are NOT summed over ranks (the helpers of the SDE trainers above are not wired in)."""
 
-    def __init__(self, model, lr=0.01, learn_noise=False, transform="softplus"):
+    def __init__(self, model, lr=0.01, learn_noise=False, transform="softplus", input_data=None):
         from . import hyper
         if transform not in hyper.TRANSFORMS:
             raise ValueError(f"transform must be one of {tuple(hyper.TRANSFORMS)}, got {transform!r}")
         self.model = model
+        self._sparse = hasattr(model, "elbo_and_grad")
+        if self._sparse and input_data is None:
+            raise ValueError(f"{type(model).__name__} is trained on its ELBO: pass input_data=(time_points, observations)")
+        if self._sparse and learn_noise:
+            raise ValueError("learn_noise needs a model with log_likelihood_and_grad()")
+        self.input_data = input_data
         self.kernel = model._kernel
         hyper.check_supported(self.kernel)
         self.learn_noise = bool(learn_noise)
@@ -505,7 +513,7 @@ class KernelHyperTrainer:
         """One Adam step; returns the loss (negative log marginal likelihood) BEFORE the step as a float."""
         import numpy as np
         from . import hyper
-        out = self.model.log_likelihood_and_grad()
+        out = self.model.elbo_and_grad(self.input_data) if self._sparse else self.model.log_likelihood_and_grad()
         loss = -float(out[0])
         values = hyper.flatten(self.kernel.hyperparameter_values())
         grads = hyper.flatten(out[1])
@@ -542,6 +550,9 @@ class KernelHyperTrainer:
         losses = []
         for _ in range(int(n_steps)):
             for _ in range(int(site_updates)):
-                self.model.update_sites()
+                if self._sparse:
+                    self.model.update_sites(self.input_data)
+                else:
+                    self.model.update_sites()
             losses.append(self.step())
         return losses
