@@ -1064,6 +1064,54 @@ int mfgm_ml_site_update(const mfgm_ml_data* data, const double* g1, const double
 int mfgm_ml_site_update_q(const mfgm_ml_data* data, const double* g1, const double* g2, double lr, double* nat1, double* nat2q,
                           void* stream);
 
+/* ---- panel sparse CVI: B independent series on one kernel, inducing grid and likelihood (panel_variational_cvi.py; csrc/mfgm_panel.h) ---
+ * The three local passes of sparse CVI (mfgm_sparse_theta / mfgm_sparse_predict + the likelihood / mfgm_sparse_site_update) for B chains
+ * side by side on the PACKED arrays of a B-chain lane-per-segment plan (d <= 8): sites nat1 [B, M + 1, 2d], nat2 [B, M + 1, 2d, 2d]
+ * (dense, symmetric), a rectangular [B, N] block of data points per series.  Device pointers. */
+typedef struct mfgm_panel_data {
+    int B, M, d, N;            /* series, inducing states per series, state dim, points per series (rectangular) */
+    const int* idx;            /* [B, N]  interval 0..M of each point (interval m lies between inducing states m-1 and m, as mfgm_sparse_data) */
+    const int* seg;            /* [B, M + 2] CSR offsets of the points of series b per interval, relative to the row; needed by the site
+                                  update only (points sorted by interval within a row); may be NULL for prediction */
+    const double* w;           /* [B, N, 2d]  H P_i  */
+    const double* c;           /* [B, N]      H T_i H^T */
+    const double* prior_mean;  /* [d]    shared */
+    const double* prior_cov;   /* [d, d] shared */
+} mfgm_panel_data;
+/* Posterior naturals of every series, packed:  with T = M = the plan's T and the prior's natural-layout blocks plin [M, d] (may be NULL:
+ * zero), pdiag [M, d, d] (lower triangle read), psub [M, d, d] (block t couples states t + 1 and t; the last one is not read) SHARED by
+ * every series,
+ *     diag_t = pdiag_t + nat2[b][t+1][:d,:d] + nat2[b][t][d:,d:],   sub_t = psub_t + 2 nat2[b][t+1][d:,:d]  (t < T - 1),
+ *     lin_t  = plin_t + nat1[b][t+1][:d] + nat1[b][t][d:]
+ * (the overlap-add of mfgm_sparse_theta, the same order of summation) written straight into the packed lin (VEC), diag (SYM), sub (FULL)
+ * of the plan: chain b, node t at lane b P + t / R, step t mod R.  Every position of the three arrays is written: padding and the
+ * sub-diagonal block of the last node get zeros, as mfgm_pack leaves them.  What mfgm_packed_factor_form takes with aD = -2, aS = -1. */
+int mfgm_panel_theta(const mfgm_plan* plan, const double* nat1, const double* nat2, const double* plin, const double* pdiag,
+                     const double* psub, double* lin, double* diag, double* sub, void* stream);
+/* Per point i of series b in interval m = idx[b, i] (values outside 0 .. M are clamped), with pmu / PC the mean / covariance of the pair
+ * (state m - 1, state m) of series b assembled from the packed x (VEC), Sig (SYM), Sub (FULL, Sigma_{t+1,t} at t) that
+ * mfgm_packed_selinv_form left on this plan -- the prior's mean / covariance at m = 0 and m = M, zero cross block there, as
+ * mfgm_sparse_predict assembles them:
+ *     fmu = w_i . pmu,   fvar = c_i + w_i^T PC w_i       (fvar <= 0 is not clamped)
+ * and from those very values VE_i, g1 = dVE/dmu - 2 (dVE/dv) fmu, g2 = dVE/dv of the likelihood `kind`: 0 (prediction only: y, ve, g1,
+ * g2 and ve_series must be NULL), MFGM_LIK_GAUSSIAN (param = variance; the formula of the readout section above), MFGM_LIK_BERNOULLI,
+ * MFGM_LIK_POISSON (mfgm_scalar_lik).  A NaN observation is an absent point: ve = g1 = g2 = 0 exactly, fmu / fvar still written --
+ * this is how ragged series are given.  ve_series [B] = the row's sum of VE_i in a fixed order (0 for N = 0).  y and the outputs fmu,
+ * fvar, ve, g1, g2 are [B, N]; any output may be NULL and is then not written.  One workgroup per series, one lane per point. */
+int mfgm_panel_predict_lik(const mfgm_plan* plan, const mfgm_panel_data* data, int kind, double param, const double* y, const double* x,
+                           const double* Sig, const double* Sub, double* fmu, double* fvar, double* ve, double* g1, double* g2,
+                           double* ve_series, void* stream);
+/* In place, with the sums over the points seg[b, m] .. seg[b, m + 1] of row b (an empty interval, or N = 0, decays the site):
+ *     nat1[b][m][r]    <- (1 - lr) old + lr sum_i g1[b, i] w_ir
+ *     nat2[b][m][r][c] <- (1 - lr) old + lr sum_i g2[b, i] (w_ir w_ic)        both triangles written, (r, c) and (c, r) the same bits.
+ * One owner per entry.
+ * All three entry points: fp64, d <= 8 and lane-per-segment plans only, no allocation, no host synchronisation (graph-capturable), no
+ * atomics: two launches on the same inputs agree bit for bit.  They return 1 before any launch for d outside 1 .. 8, a wide plan or a
+ * plan whose B, T, d differ from data's B, M, d, an unknown kind or a parameter out of range (the ranges of mfgm_scalar_lik /
+ * mfgm_pep_sites), lr outside [0, 1], or a missing pointer when there is a point to cover. */
+int mfgm_panel_site_update(const mfgm_panel_data* data, const double* g1, const double* g2, double lr, double* nat1, double* nat2,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

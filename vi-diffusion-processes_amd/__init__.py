@@ -17,4 +17,7 @@ def __getattr__(name):
     if name == "MultiLatentSparseCVI":
         from .multi_latent_variational import MultiLatentSparseCVI
         return MultiLatentSparseCVI
+    if name == "PanelSparseCVI":
+        from .panel_variational_cvi import PanelSparseCVI
+        return PanelSparseCVI
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -167,6 +167,9 @@ EXPORTS = {
     "mfgm_ml_predict_lik": (ctypes.c_int, [ctypes.c_void_p] * 12),
     "mfgm_ml_site_update": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
     "mfgm_ml_site_update_q": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
+    "mfgm_panel_theta": (ctypes.c_int, [ctypes.c_void_p] * 10),
+    "mfgm_panel_predict_lik": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 11),
+    "mfgm_panel_site_update": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
 }
 
 
@@ -222,6 +225,13 @@ class MlLik(ctypes.Structure):
 
 
 ML_NONE, ML_MULTISTAGE, ML_HETGAUSS = 0, 1, 2
+
+
+class PanelData(ctypes.Structure):
+    """mfgm_panel_data (include/mfgm.h)."""
+    _fields_ = [("B", ctypes.c_int), ("M", ctypes.c_int), ("d", ctypes.c_int), ("N", ctypes.c_int), ("idx", ctypes.c_void_p),
+                ("seg", ctypes.c_void_p), ("w", ctypes.c_void_p), ("c", ctypes.c_void_p), ("prior_mean", ctypes.c_void_p),
+                ("prior_cov", ctypes.c_void_p)]
 
 
 class KfSites(ctypes.Structure):

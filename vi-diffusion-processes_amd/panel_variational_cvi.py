@@ -1,0 +1,413 @@
+"""
+Sparse CVI on a panel: `PanelSparseCVI` fits B independent series that share one kernel, one inducing grid of M states and one scalar
+likelihood -- the per-store counts, per-sensor rates and per-subject outcomes that the single-chain SparseCVIGaussianProcess
+(sparse_variational_cvi.py) would take one Python model per series for.  Sites on pairs of consecutive inducing states, one set per
+series: nat1 [B, M + 1, 2d], nat2 [B, M + 1, 2d, 2d].
+
+Data: (time_points [B, N], observations [B, N, 1]), rectangular; the times of a row sorted along the last axis; a NaN observation is an
+absent point (zero gradients, zero variational expectation): this is how ragged series are given.
+
+Routes.  Native (CUDA tensors, state dimension <= 8, Gaussian / Bernoulli / Poisson): per step mfgm_panel_theta (sites -> packed
+posterior naturals of the B-chain plan) -> Plan.factor -> Plan.selinv -> mfgm_panel_predict_lik (marginals at the data, likelihood,
+gradients, per-series VE sums) -> mfgm_panel_site_update; the predict pass is cached on the sites' Stamp, so the ELBO of one iteration
+serves the update of the next.  Torch (anything else: d > 8, an LEG kernel, any other ScalarQuadratureLikelihood, VIDP_NATIVE_PANEL=0,
+CPU tensors): the same quantities with batched torch ops -- on the device around the same factorisation and selected inverse, on CPU
+tensors around a dense posterior over all inducing states of every series (small models, the host tests); the correctness anchor.
+"""
+import ctypes
+import os
+
+import torch
+
+from . import _lib
+from ._lib import FULL, SYM, VEC
+from .kernels import LatentExponentiallyGenerated, PiecewiseKernel
+from .likelihoods import Bernoulli, Gaussian, Poisson
+from .packed import _ptr, _stream
+from .sparse_pep import _cond_stats
+from .spatio_temporal_variational import SpatioTemporalSparseCVI
+from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
+from .stamps import Stamp
+
+_KINDS = {Gaussian: _lib.LIK_GAUSSIAN, Bernoulli: _lib.LIK_BERNOULLI, Poisson: _lib.LIK_POISSON}
+
+
+def _has_kernel(kernel, cls):
+    return isinstance(kernel, cls) or any(_has_kernel(k, cls) for k in getattr(kernel, "kernels", ()))
+
+
+class PanelSparseCVI:
+    """kernel: one kernel shared by every series (time-invariant scalar emission); inducing_points [M] (sorted, shared, M >= 2);
+    likelihood: a scalar likelihood of vidp_amd.likelihoods; num_series: B."""
+
+    CHUNK = 1 << 18          # points whose [2d, 2d] pair covariances / outer products the torch route materialises at a time
+
+    def __init__(self, kernel, inducing_points, likelihood, num_series, learning_rate=0.1, mean_function=None, shard=None):
+        if mean_function is not None:
+            raise NotImplementedError("PanelSparseCVI does not take a mean function (mean_function=): out of scope")
+        if shard is not None:
+            raise NotImplementedError("PanelSparseCVI does not share its chains between processes (shard=): out of scope")
+        if isinstance(kernel, (list, tuple)):
+            raise NotImplementedError("one kernel shared by every series; per-series kernels are out of scope")
+        if _has_kernel(kernel, PiecewiseKernel):
+            raise NotImplementedError("PanelSparseCVI does not take a PiecewiseKernel: out of scope")
+        if inducing_points.dim() != 1:
+            raise NotImplementedError("one inducing grid [M] shared by every series; per-series inducing grids are out of scope")
+        if int(inducing_points.shape[0]) < 2:
+            raise ValueError("PanelSparseCVI needs at least two inducing points")
+        if int(num_series) < 1:
+            raise ValueError("num_series must be at least 1")
+        self._kernel, self._likelihood = kernel, likelihood
+        self.learning_rate = learning_rate
+        self.inducing_inputs = inducing_points
+        self.num_series = int(num_series)
+        B, M, d = self.num_series, int(inducing_points.shape[0]), kernel.state_dim
+        dev = inducing_points.device
+        self._version = 0          # bumped by every site update: keys the cached posterior marginals
+        self.nat1 = torch.zeros((B, M + 1, 2 * d), dtype=torch.float64, device=dev)
+        self.nat2 = torch.zeros((B, M + 1, 2 * d, 2 * d), dtype=torch.float64, device=dev)
+        self._dist_p = None
+
+    # the sites are public tensors, as the single-chain model's: assigning them, or editing them in place through torch, moves the key
+    # of every cached posterior quantity (the library's own in-place updates bump `_version`)
+    @property
+    def nat1(self):
+        return self._nat1
+
+    @nat1.setter
+    def nat1(self, value):
+        self._nat1 = value
+        self._version += 1
+
+    @property
+    def nat2(self):
+        return self._nat2
+
+    @nat2.setter
+    def nat2(self, value):
+        self._nat2 = value
+        self._version += 1
+
+    def _key(self):
+        return Stamp(self._version, self._nat1, self._nat2)
+
+    def _current(self, stamp):
+        return stamp.matches(self._version, self._nat1, self._nat2)
+
+    @property
+    def kernel(self):
+        return self._kernel
+
+    @property
+    def likelihood(self):
+        return self._likelihood
+
+    # ---- routes ----------------------------------------------------------------------------------------------------------------------------
+    def _on_device(self):
+        return self.inducing_inputs.is_cuda
+
+    def _native(self):
+        return (self._on_device() and self._kernel.state_dim <= 8 and type(self._likelihood) in _KINDS
+                and not _has_kernel(self._kernel, LatentExponentiallyGenerated) and os.environ.get("VIDP_NATIVE_PANEL", "1") != "0"
+                and self._nat1.is_contiguous() and self._nat2.is_contiguous())
+
+    _dense_prior = SpatioTemporalSparseCVI._dense_prior
+    _need_device = SpatioTemporalSparseCVI._need_device
+
+    # ---- per-data-set constants ------------------------------------------------------------------------------------------------------------
+    def _features(self, t, need_sorted):
+        """dict(w [B, n, 2d], c [B, n], idx [B, n] int64 (+ int32 copy and the CSR offsets seg [B, M + 2] when sorted)) of the time
+        points t [B, n]."""
+        B, M, d = self.num_series, int(self.inducing_inputs.shape[0]), self._kernel.state_dim
+        if t.dim() != 2 or t.shape[0] != B:
+            raise ValueError(f"time points must be [num_series = {B}, n]; got {tuple(t.shape)}")
+        if t.dtype != torch.float64 or t.device != self.inducing_inputs.device:
+            raise ValueError("time points must be float64 on the model's device")
+        if bool(torch.isnan(t).any()):
+            raise ValueError("a time point is NaN: absent points are given by NaN observations, their times stay finite")
+        n = int(t.shape[1])
+        is_sorted = n < 2 or bool((t[:, 1:] >= t[:, :-1]).all())
+        if need_sorted and not is_sorted:
+            raise ValueError("the time points of every series must be sorted along the last axis")
+        z = self.inducing_inputs
+        if n > 0:
+            P, Tc, idx = _cond_stats(t.reshape(-1).contiguous(), z, self._kernel)
+            H = self._kernel.generate_emission_model(z[:1]).emission_matrix[0].to(z.device, torch.float64)      # [1, d], time-invariant
+            if H.shape[0] != 1:
+                raise NotImplementedError("PanelSparseCVI takes a kernel with one output")
+            w = (H @ P)[:, 0, :].reshape(B, n, 2 * d).contiguous()
+            c = (H @ Tc @ H.transpose(-1, -2))[:, 0, 0].reshape(B, n).contiguous()
+            idx = idx.reshape(B, n)
+        else:
+            mk = lambda *s: torch.zeros(s, dtype=torch.float64, device=z.device)
+            w, c, idx = mk(B, 0, 2 * d), mk(B, 0), torch.zeros((B, 0), dtype=torch.int64, device=z.device)
+        f = dict(w=w, c=c, idx=idx, n=n, sorted=is_sorted)
+        if self._on_device():
+            f["idx32"] = idx.to(torch.int32).contiguous()
+            if is_sorted:
+                cnt = torch.zeros((B, M + 1), dtype=torch.int64, device=z.device).scatter_add_(1, idx, torch.ones_like(idx))
+                seg = torch.zeros((B, M + 2), dtype=torch.int32, device=z.device)
+                seg[:, 1:] = torch.cumsum(cnt, 1).to(torch.int32)
+                f["seg"] = seg
+            f["pm"] = self._kernel.initial_mean(()).to(z.device, torch.float64).contiguous()
+            f["pc"] = self._kernel.initial_covariance(z[:1]).to(z.device, torch.float64).contiguous()
+            sd = _lib.PanelData()
+            sd.B, sd.M, sd.d, sd.N = B, M, d, n
+            sd.idx, sd.seg = f["idx32"].data_ptr(), (f["seg"].data_ptr() if is_sorted else None)
+            sd.w, sd.c, sd.prior_mean, sd.prior_cov = w.data_ptr(), c.data_ptr(), f["pm"].data_ptr(), f["pc"].data_ptr()
+            f["struct"] = sd
+        return f
+
+    def _data(self, input_data):
+        """The constants of a training set (sorted rows), cached on the time-point tensor."""
+        t = input_data[0]
+        c = getattr(self, "_data_cache", None)
+        if c is not None and c[0].matches(t):
+            return c[1]
+        val = self._features(t, need_sorted=True)
+        self._data_cache = (Stamp(t), val)
+        return val
+
+    def _observations(self, data, Y):
+        """dict(y [B, N] contiguous, absent [B, N] bool, y_safe [B, N, 1] with the absent points replaced by 1) per observation tensor."""
+        c = data.get("obs")
+        if c is not None and c[0].matches(Y):
+            return c[1]
+        B, N = self.num_series, data["n"]
+        if tuple(Y.shape) != (B, N, 1) or Y.dtype != torch.float64 or Y.device != self.inducing_inputs.device:
+            raise ValueError(f"observations must be a float64 [{B}, {N}, 1] tensor on the model's device")
+        y = Y[..., 0].contiguous()
+        absent = torch.isnan(y)
+        val = dict(y=y, absent=absent, y_safe=torch.where(absent, torch.ones_like(y), y)[..., None].contiguous())
+        data["obs"] = (Stamp(Y), val)
+        return val
+
+    # ---- prior -----------------------------------------------------------------------------------------------------------------------------
+    @property
+    def dist_p(self):
+        """The prior of the B series at the inducing points: a batch-B StateSpaceModel (the same chain B times)."""
+        self._need_device("dist_p")
+        if self._dist_p is None:
+            z = self.inducing_inputs
+            self._dist_p = self._kernel.state_space_model(z[None].expand(self.num_series, -1).contiguous())
+        return self._dist_p
+
+    def _prior_natural(self):
+        """Prior naturals packed on the B-chain plan (+ sum log chol [B]) and the natural-layout blocks of one chain, which every
+        series shares: lin [M, d], diag [M, d, d], sub [M, d, d] (the last block zero)."""
+        if getattr(self, "_pn", None) is None:
+            p = self.dist_p
+            pl, T, d = p.plan, p.T, p.d
+            nat = pl.ssm_to_naturals(p.packed.A, p.packed.off, p.packed.chol, want_logdet=True)
+            lin, diag = pl.unpack(VEC, nat["lin"])[0], pl.unpack(SYM, nat["diag"])[0]
+            sub = torch.zeros((T, d, d), dtype=torch.float64, device=pl.device)
+            sub[:T - 1] = pl.unpack(FULL, nat["sub"], T - 1)[0]
+            zero = bool((p._mu0 == 0).all() and (p._b == 0).all())
+            self._pn = dict(nat=nat, lin=lin.contiguous(), diag=diag.contiguous(), sub=sub.contiguous(),
+                            mean=pl.zeros(VEC) if zero else p._posterior_packed()["s"]["x"])
+        return self._pn
+
+    # ---- posterior marginals of the inducing states ------------------------------------------------------------------------------------------
+    def _theta(self):
+        """Posterior naturals of the current sites, packed (lin, diag, sub) on the B-chain plan."""
+        pl, pn = self.dist_p.plan, self._prior_natural()
+        b = self.__dict__.setdefault("_theta_bufs", {})
+        if not b:
+            b.update(lin=pl.empty(VEC), diag=pl.empty(SYM), sub=pl.empty(FULL))
+        if self._native():
+            _lib.check(pl.lib.mfgm_panel_theta(pl.h, _ptr(self._nat1), _ptr(self._nat2), _ptr(pn["lin"]), _ptr(pn["diag"]), _ptr(pn["sub"]),
+                                               _ptr(b["lin"]), _ptr(b["diag"]), _ptr(b["sub"]), _stream()), "mfgm_panel_theta")
+            return b["lin"], b["diag"], b["sub"]
+        T, d = pl.T, pl.d
+        n1, n2 = self._nat1, self._nat2
+        lin = pn["lin"] + n1[:, 1:, :d] + n1[:, :-1, d:]
+        diag = pn["diag"] + n2[:, 1:, :d, :d] + n2[:, :-1, d:, d:]
+        sub = pn["sub"][:T - 1] + 2.0 * n2[:, 1:T, d:, :d]
+        return pl.pack(VEC, lin, out=b["lin"]), pl.pack(SYM, diag, out=b["diag"]), pl.pack(FULL, sub, out=b["sub"])
+
+    def _marginals(self):
+        """One factorisation + selected inverse of the B chains for the current sites, cached until the sites move: dict(packed Sig /
+        Sub / x, log|L| [B])."""
+        m = getattr(self, "_marg", None)
+        if m is not None and self._current(m["version"]):
+            return m
+        pl = self.dist_p.plan
+        bufs = self.__dict__.setdefault("_sweep_bufs", dict(f={}, s={}))
+        lin, diag, sub = self._theta()
+        f = pl.factor(diag, sub, lin, aD=-2.0, aS=-1.0, aR=1.0, want_logdet=True, out=bufs["f"])
+        bufs["f"].update(L=f["L"], G=f["G"], y=f["y"])
+        s = pl.selinv(f["L"], f["G"], f["y"], want_sub=True, out=bufs["s"], form=f["form"])
+        bufs["s"].update(Sig=s["Sig"], Sub=s["Sub"], x=s["x"])
+        self._marg = dict(version=self._key(), packed=s, logdetL=f["logdet"])
+        return self._marg
+
+    def _dense_posterior(self):
+        """CPU tensors: (precision [B, Md, Md], mean [B, Md], covariance [B, Md, Md]) of all inducing states of every series."""
+        c = getattr(self, "_dense_q", None)
+        if c is not None and self._current(c[0]):
+            return c[1]
+        B, d, M = self.num_series, self._kernel.state_dim, int(self.inducing_inputs.shape[0])
+        b = torch.zeros((B, (M + 2) * d), dtype=torch.float64)
+        Q = torch.zeros((B, (M + 2) * d, (M + 2) * d), dtype=torch.float64)
+        for m in range(M + 1):
+            sl = slice(m * d, (m + 2) * d)
+            b[:, sl] += self._nat1[:, m]
+            Q[:, sl, sl] += -2.0 * self._nat2[:, m]
+        P = self._dense_prior()["P"] + Q[:, d:-d, d:-d]
+        S = torch.linalg.inv(P)
+        val = (P, (S @ b[:, d:-d, None])[..., 0], S)
+        self._dense_q = (self._key(), val)
+        return val
+
+    def _pair_marginals(self):
+        """Means [B, M + 1, 2d] and covariances [B, M + 1, 2d, 2d] of the pairs of consecutive inducing states of every series, the
+        prior's initial state at both ends (torch route)."""
+        B, d, M = self.num_series, self._kernel.state_dim, int(self.inducing_inputs.shape[0])
+        if self._on_device():
+            pl, s = self.dist_p.plan, self._marginals()["packed"]
+            mu, Sig, Sub = pl.unpack(VEC, s["x"]), pl.unpack(SYM, s["Sig"]), pl.unpack(FULL, s["Sub"], M - 1)
+        else:
+            _, mq, S = self._dense_posterior()
+            mu, blk, ar = mq.view(B, M, d), S.view(B, M, d, M, d), torch.arange(M)
+            Sig, Sub = blk[:, ar, :, ar, :].transpose(0, 1), blk[:, ar[1:], :, ar[:-1], :].transpose(0, 1)
+        dev = mu.device
+        pm = self._kernel.initial_mean(()).to(dev, torch.float64).expand(B, 1, d)
+        pc = self._kernel.initial_covariance_matrix().to(dev, torch.float64).expand(B, 1, d, d)
+        em, ec = torch.cat([pm, mu, pm], 1), torch.cat([pc, Sig, pc], 1)
+        zero = torch.zeros_like(pc)
+        es = torch.cat([zero, Sub, zero], 1)
+        top = torch.cat([ec[:, :-1], es.transpose(-1, -2)], -1)
+        bot = torch.cat([es, ec[:, 1:]], -1)
+        return torch.cat([em[:, :-1], em[:, 1:]], -1), torch.cat([top, bot], -2)
+
+    def _kl(self):
+        """KL[q_b || p] per series, [B]."""
+        if not self._on_device():
+            pr = self._dense_prior()
+            P, mq, S = self._dense_posterior()
+            n = mq.shape[-1]
+            return 0.5 * ((pr["P"] * S).sum((-1, -2)) + torch.einsum("bi,ij,bj->b", mq, pr["P"], mq) - n - pr["logdet"]
+                          + torch.linalg.slogdet(P)[1])
+        m, pn, p = self._marginals(), self._prior_natural(), self.dist_p
+        s = m["packed"]
+        tr, mh = p.plan.kl_terms(s["Sig"], s["Sub"], s["x"], pn["nat"]["diag"], pn["nat"]["sub"], pn["mean"], aD=-2.0, aS=-1.0)
+        return 0.5 * (tr + mh - float(p.T * p.d) + 2.0 * pn["nat"]["sumlogchol"] + 2.0 * m["logdetL"])
+
+    # ---- the predict pass ------------------------------------------------------------------------------------------------------------------
+    def _rows(self, n):
+        return max(1, self.CHUNK // max(n, 1))
+
+    def _predict_torch(self, f):
+        """(fmu, fvar) [B, n] at the points of `f` from the pair marginals, with batched torch ops."""
+        pm, pc = self._pair_marginals()
+        w, idx = f["w"], f["idx"]
+        fmu, fvar = torch.empty_like(f["c"]), f["c"].clone()
+        for lo in range(0, self.num_series, self._rows(f["n"])):          # the pair covariances are gathered a block of series at a time
+            sl = slice(lo, lo + self._rows(f["n"]))
+            rows = torch.arange(pm[sl].shape[0], device=w.device)[:, None]
+            fmu[sl] = (w[sl] * pm[sl][rows, idx[sl]]).sum(-1)
+            fvar[sl] += torch.einsum("bni,bnij,bnj->bn", w[sl], pc[sl][rows, idx[sl]], w[sl])
+        return fmu, fvar
+
+    def _predict_native(self, f, kind, param, y, want):
+        """mfgm_panel_predict_lik at the points of `f`: the outputs named in `want`, [B, n] each (ve_series [B])."""
+        pl = self.dist_p.plan
+        s = self._marginals()["packed"]
+        B, n = self.num_series, f["n"]
+        out = {k: torch.empty((B,) if k == "ve_series" else (B, n), dtype=torch.float64, device=pl.device) for k in want}
+        p = lambda k: _ptr(out.get(k))
+        _lib.check(pl.lib.mfgm_panel_predict_lik(pl.h, ctypes.byref(f["struct"]), int(kind), float(param), _ptr(y), _ptr(s["x"]),
+                                                 _ptr(s["Sig"]), _ptr(s["Sub"]), p("fmu"), p("fvar"), p("ve"), p("g1"), p("g2"),
+                                                 p("ve_series"), _stream()), "mfgm_panel_predict_lik")
+        return out
+
+    def _predict_lik(self, input_data):
+        """dict(fmu, fvar, g1, g2 [B, N], ve_series [B]) at the data for the current sites, cached until the sites, the data set or the
+        observations move."""
+        data = self._data(input_data)
+        Y = input_data[1]
+        c = getattr(self, "_pred_cache", None)
+        if c is not None and self._current(c[0]) and c[1] is data and c[2].matches(Y):
+            return c[3]
+        obs = self._observations(data, Y)
+        if self._native():
+            lik = self._likelihood
+            param = lik.variance if isinstance(lik, Gaussian) else lik.param
+            res = self._predict_native(data, _KINDS[type(lik)], param, obs["y"], ("fmu", "fvar", "g1", "g2", "ve_series"))
+        else:
+            fmu, fvar = self._predict_torch(data)
+            lik, ys, absent = self._likelihood, obs["y_safe"], obs["absent"]
+            zero = torch.zeros_like(fmu)
+            ve = lik.variational_expectations(fmu[..., None], fvar[..., None], ys).reshape(fmu.shape)
+            g1, g2 = lik.ve_gradients_expectation(fmu[..., None], fvar[..., None], ys)
+            res = dict(fmu=fmu, fvar=fvar, g1=torch.where(absent, zero, g1.reshape(fmu.shape)),
+                       g2=torch.where(absent, zero, g2.reshape(fmu.shape)), ve_series=torch.where(absent, zero, ve).sum(-1))
+        self._pred_cache = (self._key(), data, Stamp(Y), res)
+        return res
+
+    # ---- public interface ------------------------------------------------------------------------------------------------------------------
+    def update_sites(self, input_data):
+        """theta_bm <- (1 - rho) theta_bm + rho sum_{i in interval m of series b} (g1_i w_i, g2_i w_i w_i^T)."""
+        data = self._data(input_data)
+        r = self._predict_lik(input_data)
+        lr = float(self.learning_rate)
+        if self._native():
+            lib = self.dist_p.plan.lib
+            _lib.check(lib.mfgm_panel_site_update(ctypes.byref(data["struct"]), _ptr(r["g1"]), _ptr(r["g2"]), lr, _ptr(self._nat1),
+                                                  _ptr(self._nat2), _stream()), "mfgm_panel_site_update")
+            self._version += 1
+            return
+        B, M1, d2, n = self.num_series, self._nat1.shape[1], self._nat1.shape[2], data["n"]
+        w, idx = data["w"], data["idx"]
+        s1 = torch.zeros_like(self._nat1).view(B * M1, d2)
+        s2 = torch.zeros_like(self._nat2).view(B * M1, d2, d2)
+        for lo in range(0, B, self._rows(n)):
+            sl = slice(lo, lo + self._rows(n))
+            flat = (idx[sl] + M1 * torch.arange(lo, lo + idx[sl].shape[0], device=idx.device)[:, None]).reshape(-1)
+            ws = w[sl].reshape(-1, d2)
+            s1.index_add_(0, flat, r["g1"][sl].reshape(-1, 1) * ws)
+            s2.index_add_(0, flat, r["g2"][sl].reshape(-1, 1, 1) * ws[:, :, None] * ws[:, None, :])
+        self.nat1 = (1 - lr) * self._nat1 + lr * s1.view_as(self._nat1)      # (the setters move the stamps)
+        self.nat2 = (1 - lr) * self._nat2 + lr * s2.view_as(self._nat2)
+
+    def elbo_per_series(self, input_data):
+        """[B]: sum_i E_q log p(y_bi | f_bi) - KL[q_b(s_Z) || p(s_Z)] of every series."""
+        return self._predict_lik(input_data)["ve_series"] - self._kl()
+
+    def classic_elbo(self, input_data):
+        """The bound of the panel: the sum of elbo_per_series, a scalar."""
+        return self.elbo_per_series(input_data).sum()
+
+    elbo = classic_elbo
+
+    def loss(self, input_data):
+        return -self.classic_elbo(input_data)
+
+    def elbo_and_grad(self, input_data):
+        raise NotImplementedError("elbo_and_grad is not implemented for PanelSparseCVI: out of scope (DESIGN.md section 22)")
+
+    @property
+    def dist_q(self):
+        """Prior naturals + overlap-added site naturals of every series as a batch-B StateSpaceModel."""
+        p = self.dist_p
+        lin, diag, sub = (x.clone() for x in self._theta())      # _theta() reuses its buffers
+        q = naturals_to_ssm_params_packed(p.plan, lin, diag, sub)
+        q.batch_shape = p.batch_shape
+        return q
+
+    def predict_f(self, time_points):
+        """Marginal (means, variances) [B, n, 1] of f at time_points [B, n], in any order within a row."""
+        c = getattr(self, "_data_cache", None)
+        f = c[1] if c is not None and c[0].matches(time_points) else self._features(time_points, need_sorted=False)
+        if self._native():
+            r = self._predict_native(f, 0, 0.0, None, ("fmu", "fvar"))
+            fmu, fvar = r["fmu"], r["fvar"]
+        else:
+            fmu, fvar = self._predict_torch(f)
+        return fmu[..., None], fvar[..., None]
+
+    def predict_log_density(self, input_data):
+        """log p(y* | data) per point, [B, n]: the likelihood's predict_log_density of predict_f."""
+        X, Y = input_data
+        fm, fv = self.predict_f(X)
+        return self._likelihood.predict_log_density(fm, fv, Y).reshape(fm.shape[:2])
