@@ -304,6 +304,24 @@ int mfgm_cq_factor_stage(const mfgm_plan* plan, int stage, const mfgm_cq_state* 
  * the caller scales d_off / s_off by (1 - lr)).  only_level 0: the level-0 kernel alone (+ its fix-up), < 0: every level. */
 int mfgm_cq_selinv_girsanov(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L, const double* y,
                             const mfgm_sde_params* prm, double* dyn_out, void* ws, void* stream);
+/* TWO factorisations of one dyn in one call: q (sites A) -> L, y, logdet / quad and q_next (the same dyn, slot, offsets and p0_off
+ * with other site_lin / site_sym: sites B) -> L2, y2.  In the CVI-DP loop these are the factorisation behind the ELBO of step n and the
+ * one behind update_girsanov_sites of step n + 1.  The levels above the finest one -- a latency-bound chain of dependent block steps --
+ * run ONCE at double width: A in the plan's own coarse levels, B in the second copy of them the workspace of such plans holds; the two
+ * level-0 forward sweeps are the two wavefronts of one workgroup per tile (d <= 6: the records are read once; d = 7, 8: two sweeps).
+ * The call ends with the joint coarse backward pass, so the backward sweeps that follow need only_level = 0: mfgm_cq_selinv_kl on
+ * (L, y), mfgm_cq_selinv_girsanov_alt on (L2, y2).  The second copy is touched by nothing else: (L2, y2) with it stay valid across
+ * later mfgm_cq_factor calls on the plan, until the next mfgm_cq_factor_pair.  Results are those of mfgm_cq_factor on q and on q_next. */
+int mfgm_cq_factor_pair(const mfgm_plan* plan, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y, double* logdet,
+                        double* quad, double* L2, double* y2, void* ws, int* info, void* stream);
+/* one part of it alone (profiling): stage 0 the two level-0 reduces, 1 the level-0 forward pair, 2 the joint up phase of the levels
+ * above the finest one, 3 their joint backward pass -- each on whatever the stages before it left */
+int mfgm_cq_factor_pair_stage(const mfgm_plan* plan, int stage, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y,
+                              double* L2, double* y2, void* ws, int* info, void* stream);
+/* mfgm_cq_selinv_girsanov on the second factorisation of mfgm_cq_factor_pair: the separator marginals come from the second copy of
+ * the coarse levels (only_level 0: as the pair call left them; < 0: their backward pass is run again first). */
+int mfgm_cq_selinv_girsanov_alt(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L2, const double* y2,
+                                const mfgm_sde_params* prm, double* dyn_out, void* ws, void* stream);
 /* backward sweep with the KL sum (mfgm_packed_selinv_kl): marginals Sig (SYM), x (VEC) -- both NULL: not written, the ELBO needs only
  * the sums and the observation nodes --, kl_part [B]; obs_mu [n, d] / obs_cov [n, d, d] (both or neither) receive the marginals at
  * the observation nodes, in observation order.  only_level 0: the level-0 kernel alone, > 0: the levels above it alone (profiling),

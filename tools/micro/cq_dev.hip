@@ -13,3 +13,12 @@ void inst(SweepArgs a, CqArgs q, SdeParams pr, double* fix) {
     hipLaunchKernelGGL((k_backward_girsanov_cq<6>), dim3(1), dim3(64), 0, 0, a, pr, q, fix);
     hipLaunchKernelGGL((k_backward_kl_cq<6>), dim3(1), dim3(64), 0, 0, a, pr, q);
 }
+// k_forward_pair_cq at every size and cache policy the library dispatches it for
+template <int D>
+void inst_pair(SweepArgs a, CqArgs q) {
+    hipLaunchKernelGGL((k_forward_pair_cq<D>), dim3(1), dim3(128), 0, 0, a, q, a, q);
+    hipLaunchKernelGGL((k_forward_pair_cq<D, 1>), dim3(1), dim3(128), 0, 0, a, q, a, q);
+}
+void inst_pairs(SweepArgs a, CqArgs q) {
+    inst_pair<1>(a, q); inst_pair<2>(a, q); inst_pair<3>(a, q); inst_pair<4>(a, q); inst_pair<5>(a, q); inst_pair<6>(a, q);
+}

@@ -392,6 +392,87 @@ int cq_factor_impl(const Plan& P0, const CqArgs& q, double* Lg, double* yg, doub
     return 0;
 }
 
+// Two factorisations of one dyn with two sets of observation sites (q: sites A -> L, y, logdet / quad; q2: sites B -> L2, y2), the
+// levels >= 1 of both in ONE latency-bound chain at double width: A in the plan's own coarse levels, B in their second copy
+// (Plan::off_pair).  Ends with the joint coarse backward pass, so that the level-0 backward sweeps that follow (only_level = 0) find
+// the separator marginals of their factorisation in place.  Every body is the one the single route runs: same numbers.
+template <int D>
+int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double* Lg, double* yg, double* logdet, double* quad, double* L2,
+                        double* y2, double* ws, int* info, hipStream_t st, int only_stage = -1) {
+    // only_stage (profiling): 0 the two level-0 reduces, 1 the level-0 forward pair, 2 the joint up phase of the levels above, 3 their
+    // joint backward pass
+    const auto on = [&](int s) { return only_stage < 0 || only_stage == s; };
+    const int K = P.nlevels - 1;
+    const size_t sh = P.off_pair - P.off_Dhat[1];
+    double* ws2 = ws + sh;                            // (only the offsets of levels >= 1 are ever added to it)
+    SweepArgs a0;
+    memset(&a0, 0, sizeof(a0));
+    a0.lv = P.lv[0];
+    a0.info = info;
+    a0.aD = -2.0; a0.aS = -1.0; a0.aR = 1.0;
+    a0.Lg = Lg; a0.yg = yg;
+    a0.part = (logdet || quad) ? ws + P.off_part[0] : nullptr;
+    SweepArgs a1 = a0;
+    a1.Lg = L2; a1.yg = y2; a1.part = nullptr;
+    bind_up(P, 0, ws, a0);
+    bind_up(P, 0, ws2, a1);
+    dim3 grid(a0.lv.Lpad / 64), block(64);
+    if (on(0)) {
+        hipLaunchKernelGGL((k_reduce_cq<D>), grid, block, 0, st, a0, q);
+        MFGM_CHECK_LAUNCH();
+        hipLaunchKernelGGL((k_reduce_cq<D>), grid, block, 0, st, a1, q2);
+        MFGM_CHECK_LAUNCH();
+    }
+    const int lf = coarse_fuse_from(P);
+    for (int l = 1; l < K && l < lf && on(2); ++l) {
+        const SweepArgs a = coarse_level_args(P, l, ws, info), b = coarse_level_args(P, l, ws2, info);
+        hipLaunchKernelGGL((k_reduce_pair<D>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
+        MFGM_CHECK_LAUNCH();
+    }
+    if (lf <= K && on(2)) {
+        hipLaunchKernelGGL((k_coarse_factor_pair<D, true>), dim3(2 * P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p(), sh);
+        MFGM_CHECK_LAUNCH();
+    }
+    for (int l = std::min(K, lf - 1); l >= 1 && on(2); --l) {
+        const SweepArgs a = coarse_level_args(P, l, ws, info), b = coarse_level_args(P, l, ws2, info);
+        if (l < K) hipLaunchKernelGGL((k_forward_pair<D, true>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
+        else hipLaunchKernelGGL((k_forward_pair<D, false>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
+        MFGM_CHECK_LAUNCH();
+    }
+    if (!on(1)) {
+        // (profiling call for another stage)
+    } else if constexpr (D <= 6) {
+        if (a0.lv.nt >= 1) hipLaunchKernelGGL((k_forward_pair_cq<D, 1>), grid, dim3(128), 0, st, a0, q, a1, q2);
+        else hipLaunchKernelGGL((k_forward_pair_cq<D>), grid, dim3(128), 0, st, a0, q, a1, q2);
+        MFGM_CHECK_LAUNCH();
+    } else {
+        // d = 7, 8: the body does not fit 256 registers; one forward sweep after the other
+        if (a0.lv.nt >= 2) {
+            hipLaunchKernelGGL((k_forward_cq<D, 2>), grid, block, 0, st, a0, q);
+            hipLaunchKernelGGL((k_forward_cq<D, 2>), grid, block, 0, st, a1, q2);
+        } else {
+            hipLaunchKernelGGL((k_forward_cq<D>), grid, block, 0, st, a0, q);
+            hipLaunchKernelGGL((k_forward_cq<D>), grid, block, 0, st, a1, q2);
+        }
+        MFGM_CHECK_LAUNCH();
+    }
+    if (only_stage < 0 && (logdet || quad)) {
+        hipLaunchKernelGGL(k_sum_partials, dim3(P.B), dim3(256), 0, st, ws + P.off_part[0], P.lv[0].P, P.lv[0].Lpad, logdet, quad);
+        MFGM_CHECK_LAUNCH();
+    }
+    if (lf <= K && on(3)) {
+        hipLaunchKernelGGL((k_coarse_backward_pair<D, true>), dim3(2 * P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p(), sh);
+        MFGM_CHECK_LAUNCH();
+    }
+    for (int l = std::min(K, lf - 1); l >= 1 && on(3); --l) {
+        const SweepArgs a = coarse_level_args(P, l, ws, nullptr), b = coarse_level_args(P, l, ws2, nullptr);
+        if (l < K) hipLaunchKernelGGL((k_backward_pair<D, true>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
+        else hipLaunchKernelGGL((k_backward_pair<D, false>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
+        MFGM_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
 template <int D>
 int cq_coarse_backward(const Plan& P, double* ws, hipStream_t st) {
     const int K = P.nlevels - 1;
@@ -410,16 +491,18 @@ int cq_coarse_backward(const Plan& P, double* ws, hipStream_t st) {
 
 template <int D>
 int cq_selinv_girsanov_impl(const Plan& P, const CqArgs& q, const double* Lg, const double* yg, const SdeParams& pr, double* ws,
-                            hipStream_t st, int only_level) {
+                            hipStream_t st, int only_level, bool alt = false) {
+    // alt: the factorisation's levels >= 1 are the second copy (the second one of mfgm_cq_factor_pair)
+    double* wsc = alt ? ws + (P.off_pair - P.off_Dhat[1]) : ws;
     if (only_level != 0) {
-        int rc = cq_coarse_backward<D>(P, ws, st);
+        int rc = cq_coarse_backward<D>(P, wsc, st);
         if (rc) return rc;
     }
     SweepArgs a;
     memset(&a, 0, sizeof(a));
     a.lv = P.lv[0];
     a.Lg = const_cast<double*>(Lg); a.yg = const_cast<double*>(yg); a.aS = -1.0;
-    bind_up(P, 0, ws, a);
+    bind_up(P, 0, wsc, a);
     double* fix = ws + P.off_part[0];
     dim3 grid(a.lv.Lpad / 64), block(64);
     if (a.lv.nt >= 2) hipLaunchKernelGGL((k_backward_girsanov_cq<D, 2>), grid, block, 0, st, a, pr, q, fix);
@@ -686,6 +769,38 @@ int mfgm_cq_selinv_girsanov(const mfgm_plan* plan, int only_level, const mfgm_cq
     CqArgs c = cq_args(q);
     c.dyn_out = dyn_out;
     MFGM_DISPATCH_D(P.d, (cq_selinv_girsanov_impl<DD>(P, c, L, y, pr, (double*)ws, (hipStream_t)stream, only_level)));
+}
+
+int mfgm_cq_factor_pair(const mfgm_plan* plan, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y, double* logdet,
+                        double* quad, double* L2, double* y2, void* ws, int* info, void* stream) {
+    if (!cq_ok(plan, q) || !cq_ok(plan, q_next) || !L || !y || !L2 || !y2 || L2 == L || y2 == y || !ws || !info) return 1;
+    // one dyn, two sets of observation sites
+    if (plan->p.off_pair == 0 || q_next->dyn != q->dyn || q_next->slot != q->slot || q_next->p0_off != q->p0_off ||
+        q_next->d_off != q->d_off || q_next->s_off != q->s_off)
+        return 1;
+    const Plan& P = plan->p;
+    const CqArgs c = cq_args(q), c2 = cq_args(q_next);
+    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, logdet, quad, L2, y2, (double*)ws, info, (hipStream_t)stream)));
+}
+
+int mfgm_cq_factor_pair_stage(const mfgm_plan* plan, int stage, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y,
+                              double* L2, double* y2, void* ws, int* info, void* stream) {
+    if (!cq_ok(plan, q) || !cq_ok(plan, q_next) || !L || !y || !L2 || !y2 || L2 == L || y2 == y || !ws || !info) return 1;
+    if (plan->p.off_pair == 0 || q_next->dyn != q->dyn || q_next->slot != q->slot || stage < 0 || stage > 3) return 1;
+    const Plan& P = plan->p;
+    const CqArgs c = cq_args(q), c2 = cq_args(q_next);
+    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, nullptr, nullptr, L2, y2, (double*)ws, info, (hipStream_t)stream, stage)));
+}
+
+int mfgm_cq_selinv_girsanov_alt(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L2, const double* y2,
+                                const mfgm_sde_params* prm, double* dyn_out, void* ws, void* stream) {
+    if (!cq_ok(plan, q) || !L2 || !y2 || !prm || !dyn_out || !ws || dyn_out == q->dyn || prm->kind != 0 || plan->p.off_pair == 0) return 1;
+    const Plan& P = plan->p;
+    SdeParams pr;
+    memcpy(&pr, prm, sizeof(pr));
+    CqArgs c = cq_args(q);
+    c.dyn_out = dyn_out;
+    MFGM_DISPATCH_D(P.d, (cq_selinv_girsanov_impl<DD>(P, c, L2, y2, pr, (double*)ws, (hipStream_t)stream, only_level, true)));
 }
 
 int mfgm_cq_selinv_kl(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L, const double* y,

@@ -713,6 +713,23 @@ static __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2
     else reduce_cq_lds_body<D>(a, q, lane, me, lds, l);
 }
 
+// ---- the forward sweeps of TWO factorisations of one dyn as the two wavefronts of one workgroup ----------------------------------------
+// (mfgm_cq_factor_pair: the ELBO's factorisation and the next step's first one differ only in the observation sites.)  Wavefront 0 is
+// the forward sweep of a tile for (a, q), wavefront 1 that of the same tile for (a2, q2): the same dyn / slot / offsets, the other site
+// arrays, its own factor arrays and the second copy of the coarse levels for its boundary state.  Both run forward_cq_body<D, true> as
+// it is, so each gives bit for bit what k_forward_cq gives; the records are read from HBM once (the barrier every MFGM_CQ_SYNC_EVERY
+// nodes keeps the second reader within reach of the CU's L1 / the XCD's L2).  Padding lanes repeat the last live lane's work, as in
+// k_forward_reduce_cq.  D <= 6: at 7 and 8 the body does not fit the 256 registers two wavefronts per SIMD leave each.
+template <int D, int NT = 0>
+static __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_forward_pair_cq(SweepArgs a, CqArgs q, SweepArgs a2,
+                                                                                                            CqArgs q2) {
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int lane = min((int)blockIdx.x * 64 + l, a.lv.L - 1);
+    const LaneRef me{(int)blockIdx.x, lane & 63, NT >= 1 ? 1 : 0};     // streamed stores only: the second reader of a record is served from the cache
+    if (wave == 0) forward_cq_body<D, true>(a, q, lane, me);
+    else forward_cq_body<D, true>(a2, q2, lane, me);
+}
+
 // ---- backward helpers ------------------------------------------------------------------------------------------------------------
 // backward_s_left with the left separator's theta_sub rebuilt from the cq state
 template <int D>

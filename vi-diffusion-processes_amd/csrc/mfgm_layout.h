@@ -49,6 +49,8 @@ struct Plan {
     size_t off_part2;              // second-stage scratch of the split partial sums (2 * B * 128 doubles)
     size_t off_alt;                // narrow plans with >= 2 levels: a second copy of the level-1 INPUT region [off_Dhat[1], off_L[1])
                                    // (the separator system mfgm_cq_factor_pipelined makes one factorisation ahead); 0: none
+    size_t off_pair;               // narrow plans with >= 2 levels: a second copy of EVERY level >= 1, [off_Dhat[1], off_alt): the coarse
+                                   // levels of the second factorisation of mfgm_cq_factor_pair; 0: none
     size_t ws_doubles;             // total workspace size in doubles
 };
 

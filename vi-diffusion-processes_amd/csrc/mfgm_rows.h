@@ -449,8 +449,8 @@ constexpr int kRowsMaxP = kCoarseBlock / 16;
 
 // reduce l0 .. top-1, then forward top .. l0 (l0 >= 1); grid = B workgroups
 template <int D, bool HAS_RHS>
-static __global__ __launch_bounds__(kCoarseBlock) void k_coarse_factor(Plan P, int l0, double* ws, int* info, int rows_p) {
-    const int K = P.nlevels - 1, b = blockIdx.x;
+MFGM_DEV void coarse_factor_chain(const Plan& P, int l0, double* ws, int* info, int rows_p, const int b) {
+    const int K = P.nlevels - 1;
     const int g = threadIdx.x >> 4, r = threadIdx.x & 15;
     for (int l = l0; l < K; ++l) {
         const SweepArgs a = coarse_level_args(P, l, ws, info);
@@ -490,10 +490,22 @@ static __global__ __launch_bounds__(kCoarseBlock) void k_coarse_factor(Plan P, i
     }
 }
 
+template <int D, bool HAS_RHS>
+static __global__ __launch_bounds__(kCoarseBlock) void k_coarse_factor(Plan P, int l0, double* ws, int* info, int rows_p) {
+    coarse_factor_chain<D, HAS_RHS>(P, l0, ws, info, rows_p, blockIdx.x);
+}
+// Two factorisations at once (mfgm_cq_factor_pair): grid = 2 B workgroups, workgroup b >= B is chain b - B of the second copy of the
+// levels >= 1 (Plan::off_pair), `shift` doubles further on in the workspace.
+template <int D, bool HAS_RHS>
+static __global__ __launch_bounds__(kCoarseBlock) void k_coarse_factor_pair(Plan P, int l0, double* ws, int* info, int rows_p, size_t shift) {
+    const bool second = (int)blockIdx.x >= P.B;
+    coarse_factor_chain<D, HAS_RHS>(P, l0, second ? ws + shift : ws, info, rows_p, second ? (int)blockIdx.x - P.B : (int)blockIdx.x);
+}
+
 // backward top .. l0
 template <int D, bool HAS_RHS>
-static __global__ __launch_bounds__(kCoarseBlock) void k_coarse_backward(Plan P, int l0, double* ws, int rows_p) {
-    const int K = P.nlevels - 1, b = blockIdx.x;
+MFGM_DEV void coarse_backward_chain(const Plan& P, int l0, double* ws, int rows_p, const int b) {
+    const int K = P.nlevels - 1;
     const int g = threadIdx.x >> 4, r = threadIdx.x & 15;
     {
         const SweepArgs a = coarse_level_args(P, K, ws, nullptr);
@@ -519,6 +531,16 @@ static __global__ __launch_bounds__(kCoarseBlock) void k_coarse_backward(Plan P,
         }
         __syncthreads();
     }
+}
+
+template <int D, bool HAS_RHS>
+static __global__ __launch_bounds__(kCoarseBlock) void k_coarse_backward(Plan P, int l0, double* ws, int rows_p) {
+    coarse_backward_chain<D, HAS_RHS>(P, l0, ws, rows_p, blockIdx.x);
+}
+template <int D, bool HAS_RHS>
+static __global__ __launch_bounds__(kCoarseBlock) void k_coarse_backward_pair(Plan P, int l0, double* ws, int rows_p, size_t shift) {
+    const bool second = (int)blockIdx.x >= P.B;
+    coarse_backward_chain<D, HAS_RHS>(P, l0, second ? ws + shift : ws, rows_p, second ? (int)blockIdx.x - P.B : (int)blockIdx.x);
 }
 
 }  // namespace mfgm

@@ -572,6 +572,40 @@ static __global__ __launch_bounds__(64) void k_backward(SweepArgs a) {
     backward_body<D, HAS_RHS, HAS_UP, WANT_SUB, WANT_MOM, USE_S, CL>(a, lane, LaneRef{(int)blockIdx.x, (int)threadIdx.x});
 }
 
+// A level >= 1 of TWO factorisations in one launch (mfgm_cq_factor_pair): twice the tiles; tile t >= Lpad / 64 is tile t - Lpad / 64 of
+// the second system, whose arrays `a2` binds (the second copy of the levels >= 1 in the plan workspace).  The levels above the finest
+// one are bound by the latency of their dependent steps, not by lanes: double width costs about what single width does.
+template <int D>
+static __global__ __launch_bounds__(64) void k_reduce_pair(SweepArgs a, SweepArgs a2) {
+    const int tiles = a.lv.Lpad / 64;
+    const bool second = (int)blockIdx.x >= tiles;
+    const int tile = second ? (int)blockIdx.x - tiles : (int)blockIdx.x;
+    const int lane = tile * 64 + threadIdx.x;
+    if (lane >= a.lv.L) return;
+    if (second) reduce_body<D, true, true>(a2, lane, LaneRef{tile, (int)threadIdx.x});
+    else reduce_body<D, true, true>(a, lane, LaneRef{tile, (int)threadIdx.x});
+}
+template <int D, bool HAS_UP>
+static __global__ __launch_bounds__(64) void k_forward_pair(SweepArgs a, SweepArgs a2) {
+    const int tiles = a.lv.Lpad / 64;
+    const bool second = (int)blockIdx.x >= tiles;
+    const int tile = second ? (int)blockIdx.x - tiles : (int)blockIdx.x;
+    const int lane = tile * 64 + threadIdx.x;
+    if (lane >= a.lv.L) return;
+    if (second) forward_body<D, true, true, HAS_UP>(a2, lane, LaneRef{tile, (int)threadIdx.x});
+    else forward_body<D, true, true, HAS_UP>(a, lane, LaneRef{tile, (int)threadIdx.x});
+}
+template <int D, bool HAS_UP>
+static __global__ __launch_bounds__(64) void k_backward_pair(SweepArgs a, SweepArgs a2) {
+    const int tiles = a.lv.Lpad / 64;
+    const bool second = (int)blockIdx.x >= tiles;
+    const int tile = second ? (int)blockIdx.x - tiles : (int)blockIdx.x;
+    const int lane = tile * 64 + threadIdx.x;
+    if (lane >= a.lv.L) return;
+    if (second) backward_body<D, true, HAS_UP, false, false, false, true>(a2, lane, LaneRef{tile, (int)threadIdx.x});
+    else backward_body<D, true, HAS_UP, false, false, false, true>(a, lane, LaneRef{tile, (int)threadIdx.x});
+}
+
 // ---- coarse levels in one launch per pass ----------------------------------------------------------------------------------------
 // The levels above the finest one are latency-bound (few lanes, a handful of dependent steps each): launched one kernel per level
 // they cost a launch boundary and a cold start apiece (five levels x three passes per factorisation + selected inverse at the

@@ -497,9 +497,30 @@ class Plan:
                    "mfgm_cq_factor_pipelined")
         return dict(L=L, y=y, logdet=logdet)
 
-    def cq_selinv_girsanov(self, cq, L, y, prm, dyn_out, only_level=-1):
-        _lib.check(self.lib.mfgm_cq_selinv_girsanov(self.h, int(only_level), ctypes.byref(cq.struct()), _ptr(L), _ptr(y), ctypes.byref(prm),
-                                                    _ptr(dyn_out), _ptr(self.ws), _stream()), "mfgm_cq_selinv_girsanov")
+    def cq_factor_pair(self, cq, next_sites, out=None, out2=None, want_logdet=True):
+        """Two factorisations of one dyn in one call (mfgm_cq_factor_pair): that of `cq` -> dict(L, y, logdet) and that of the same
+        state with the observation sites `next_sites` = (site_lin, site_sym) -> the second dict(L, y).  The levels above the finest one
+        run once at double width; both coarse backward passes are made, so the sweeps that follow take only_level=0:
+        cq_selinv_kl on the first, cq_selinv_girsanov(alt=True) on the second."""
+        out = {} if out is None else out
+        out2 = {} if out2 is None else out2
+        L = out.get("L") if out.get("L") is not None else self.empty(TRI)
+        y = out.get("y") if out.get("y") is not None else self.empty(VEC)
+        L2 = out2.get("L") if out2.get("L") is not None else self.empty(TRI)
+        y2 = out2.get("y") if out2.get("y") is not None else self.empty(VEC)
+        self.epoch += 1
+        logdet = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
+        nxt = cq.struct()
+        nxt.site_lin, nxt.site_sym = next_sites[0].data_ptr(), next_sites[1].data_ptr()
+        _lib.check(self.lib.mfgm_cq_factor_pair(self.h, ctypes.byref(cq.struct()), ctypes.byref(nxt), _ptr(L), _ptr(y), _ptr(logdet), None,
+                                                _ptr(L2), _ptr(y2), _ptr(self.ws), _ptr(self.info), _stream()), "mfgm_cq_factor_pair")
+        return dict(L=L, y=y, logdet=logdet), dict(L=L2, y=y2)
+
+    def cq_selinv_girsanov(self, cq, L, y, prm, dyn_out, only_level=-1, alt=False):
+        """alt: (L, y) is the second factorisation of cq_factor_pair (its coarse levels are the workspace's second copy)."""
+        fn = self.lib.mfgm_cq_selinv_girsanov_alt if alt else self.lib.mfgm_cq_selinv_girsanov
+        _lib.check(fn(self.h, int(only_level), ctypes.byref(cq.struct()), _ptr(L), _ptr(y), ctypes.byref(prm),
+                      _ptr(dyn_out), _ptr(self.ws), _stream()), "mfgm_cq_selinv_girsanov_alt" if alt else "mfgm_cq_selinv_girsanov")
         return dyn_out
 
     def cq_selinv_kl(self, cq, L, y, prm, out=None, obs_mu=None, obs_cov=None, only_level=-1, want_marginals=True):

@@ -364,23 +364,33 @@ class _Ahead:
     the stamp of the state it was made FOR and, once update_data_sites has taken the prediction over, the stamp of the state the
     separator system in the plan's workspace is armed for.  Every stamp is over (site_lin, site_sym, cq, cq.version, lr, plan.epoch):
     a site written or replaced, a Girsanov update, another learning rate or another factorisation on the plan leaves no match.
+    A record has a kind: REDUCE, the level-0 reduce alone (the separator system in the workspace's second level-1 input region), or
+    PAIR, the whole factorisation (made by Plan.cq_factor_pair: `held` is its dict(L, y), its coarse levels are the workspace's second
+    copy).  `take` hands out only the kind it is asked for; a record of the other kind is dropped.
     Host bookkeeping only: the launches are the caller's (`make` is handed them as a callable)."""
+
+    REDUCE, PAIR = "reduce", "pair"
 
     def __init__(self):
         self.lr, self.bufs, self.side = None, None, None
         self.rec = None         # [stamp made for, stamp armed for | None]
+        self.kind, self.held = self.REDUCE, None
         self.consumed = 0       # records taken over by update_data_sites so far
 
     def _parts(self, lin, sym, cq, plan, lr):
         return lin, sym, cq, cq.version, float(lr), plan.epoch
 
-    def make(self, lin, cq, plan, launch):
+    def make(self, lin, cq, plan, launch, kind=REDUCE):
         """Record for the state as it is now: launch(spare_lin, spare_sym, lr) writes the predicted sites and runs the factorisation
-        that makes their separator system beside its own work; its result is handed back."""
+        that makes their separator system beside its own work; its result is handed back.  kind=PAIR: launch returns (its result,
+        the factorisation of the predicted state), and the latter is held for `take`."""
         self.drop()
         if self.bufs is None:
             self.bufs = [torch.empty_like(lin), torch.empty_like(cq.site_sym)]
         out = launch(self.bufs[0], self.bufs[1], self.lr)
+        if kind == self.PAIR:
+            out, self.held = out
+        self.kind = kind
         self.rec = [Stamp(*self._parts(lin, cq.site_sym, cq, plan, self.lr)), None]
         return out
 
@@ -396,16 +406,19 @@ class _Ahead:
             self.drop()
         return out
 
-    def take(self, lin, cq, plan):
-        """Whether a separator system was made ahead for the state as it is NOW: consumed by the next factorisation (which joins the
-        side stream itself)."""
+    def take(self, lin, cq, plan, kind=REDUCE):
+        """Whether a record of this kind was made ahead for the state as it is NOW.  REDUCE: True, consumed by the next factorisation
+        (which joins the side stream itself); PAIR: the held factorisation, dict(L, y), consumed by the next Girsanov sweep."""
         rec = self.rec
         if rec is None:
             return False
-        if rec[1] is None or not rec[1].matches(*self._parts(lin, cq.site_sym, cq, plan, self.lr)):
+        if rec[1] is None or kind != self.kind or not rec[1].matches(*self._parts(lin, cq.site_sym, cq, plan, self.lr)):
             self.drop()
             return False
         self.rec = None
+        if kind == self.PAIR:
+            held, self.held = self.held, None
+            return held
         return True
 
     def drop(self):
@@ -414,6 +427,7 @@ class _Ahead:
             if self.side is not None:
                 torch.cuda.current_stream().wait_stream(self.side)
             self.rec = None
+        self.held = None
 
 
 class CVISitesSDE(CVISitesSSM):
@@ -665,6 +679,11 @@ class CVISitesSDE(CVISitesSSM):
     # VIDP_PIPE_STREAMS=1: the reduce made ahead runs as a kernel of its own on a second stream (round 4's first form; A/B) instead of
     # as the second wavefront of the forward sweep's workgroups (k_forward_reduce_cq: the records are read once)
     pipe_two_streams = os.environ.get("VIDP_PIPE_STREAMS", "0") == "1"
+    # VIDP_PIPE_PAIR=1: not the level-0 reduce but the WHOLE first factorisation of the next step is made ahead, together with the
+    # ELBO's (Plan.cq_factor_pair): the two differ only in the observation sites, so the coarse levels -- a latency-bound chain during
+    # which the level-0 SIMDs idle -- run once per step at double width instead of twice, and the two level-0 forward sweeps share one
+    # read of the records.  One more factor buffer (L, y) is held.  0: the level-0 reduce alone is made ahead, as above.
+    pipe_pair = os.environ.get("VIDP_PIPE_PAIR", "1") != "0"
     # below this many nodes (B T) a level-0 reduce is a few microseconds: the second stream's event round trips would cost more than
     # they hide (config 1, T = 1001: 0.133 -> 0.174 ms with it)
     pipeline_min_nodes = 200000
@@ -748,16 +767,24 @@ class CVISitesSDE(CVISitesSSM):
                 # sites as the next update_data_sites(ahead.lr) will leave them go into the spare buffers (one launch)
                 if self.pipe_two_streams and ahead.side is None:
                     ahead.side = torch.cuda.Stream(device=self.device)
+                pair = self.pipe_pair and ahead.side is None
 
                 def launch(lin, sym, lr_next):
                     self._site_blend(cq, lin, sym, lr_next)
+                    if pair:
+                        # the WHOLE first factorisation of the next step with this one: the coarse levels of both in one chain
+                        f, f2 = pl.cq_factor_pair(cq, (lin, sym), out=self._bufs["f"], out2=self._bufs.setdefault("f2", {}))
+                        self._bufs["f2"].update(L=f2["L"], y=f2["y"])
+                        return f, f2
                     return pl.cq_factor(cq, want_logdet=True, out=self._bufs["f"], next_sites=(lin, sym), side=ahead.side)
-                f = ahead.make(self._data_nat1, cq, pl, launch)
+                f = ahead.make(self._data_nat1, cq, pl, launch, kind=ahead.PAIR if pair else ahead.REDUCE)
+                coarse_done = pair
             else:
                 f = pl.cq_factor(cq, want_logdet=True, out=self._bufs["f"], use_ahead=ahead.take(self._data_nat1, cq, pl), side=ahead.side)
+                coarse_done = False
             self._bufs["f"].update(L=f["L"], y=f["y"])
             s = pl.cq_selinv_kl(cq, f["L"], f["y"], self._sde_prm, out=self._bufs["s"], obs_mu=self.fx_mus_obs if obs else None,
-                                obs_cov=self.fx_covs_obs if obs else None, want_marginals=not lazy)
+                                obs_cov=self.fx_covs_obs if obs else None, want_marginals=not lazy, only_level=0 if coarse_done else -1)
             if not lazy:
                 self._bufs["s"].update(Sig=s["Sig"], x=s["x"])
             self._q = dict(logdetL=f["logdet"], mu=s["x"], Sig=s["Sig"], Sub=None, mom=None, klpart=s["klpart"], epoch=pl.epoch)
@@ -975,12 +1002,18 @@ class CVISitesSDE(CVISitesSSM):
         if cq is not None:
             # reduce -> forward -> backward sweep that writes (1 - lr) dyn + lr theta~ into the spare buffer; the uniform off-diagonals
             # scale by (1 - lr); the data sites do not enter (they are not part of the resident state)
-            f = pl.cq_factor(cq, want_logdet=False, out=self._bufs["f"], use_ahead=self._ahead.take(self._data_nat1, cq, pl),
-                             side=self._ahead.side)
-            self._bufs["f"].update(L=f["L"], y=f["y"])
+            ahead = self._ahead
+            held = ahead.take(self._data_nat1, cq, pl, kind=ahead.PAIR) if ahead.kind == ahead.PAIR else False
             if cq.spare is None:
                 cq.spare = torch.empty_like(cq.dyn)
-            pl.cq_selinv_girsanov(cq, f["L"], f["y"], self._sde_prm, cq.spare)
+            if held:
+                # this state's factorisation was made with the last ELBO's (Plan.cq_factor_pair), coarse backward pass included:
+                # only the level-0 sweep is left
+                pl.cq_selinv_girsanov(cq, held["L"], held["y"], self._sde_prm, cq.spare, only_level=0, alt=True)
+            else:
+                f = pl.cq_factor(cq, want_logdet=False, out=self._bufs["f"], use_ahead=ahead.take(self._data_nat1, cq, pl), side=ahead.side)
+                self._bufs["f"].update(L=f["L"], y=f["y"])
+                pl.cq_selinv_girsanov(cq, f["L"], f["y"], self._sde_prm, cq.spare)
             cq.dyn, cq.spare = cq.spare, cq.dyn
             cq.version += 1
             cq.d_off *= 1.0 - lr
