@@ -318,6 +318,23 @@ int mfgm_cq_factor_pair(const mfgm_plan* plan, const mfgm_cq_state* q, const mfg
  * above the finest one, 3 their joint backward pass -- each on whatever the stages before it left */
 int mfgm_cq_factor_pair_stage(const mfgm_plan* plan, int stage, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y,
                               double* L2, double* y2, void* ws, int* info, void* stream);
+/* mfgm_cq_factor_pair for observations on a regular grid.  CONTRACT: every non-negative slot entry sits at a local step of its
+ * level-0 segment that is a multiple of `stride` (stride >= 2, R % stride == 0: observation nodes that are multiples of stride, and a
+ * segment length that is one too).  The level-0 reduce forms the Schur complement of a segment's interior onto its separators, which
+ * no elimination order changes; with the observed nodes eliminated last everything before them depends on dyn and the offsets alone,
+ * so that part is made ONCE for both site sets (k_reduce_cq_interior, parked in `scratch`, mfgm_cq_heads_scratch_doubles(plan, stride)
+ * doubles) and only the R / stride steps on the observed nodes are made per site set (k_reduce_cq_heads).  Everything after the
+ * level-0 reduce is mfgm_cq_factor_pair's.  Results are those of mfgm_cq_factor_pair up to the rounding of another elimination order.
+ * `scratch_doubles` is the size of `scratch` in doubles.  Returns 1 for stride < 2, R % stride != 0, a plan without the second copy of
+ * the coarse levels, or a scratch array smaller than mfgm_cq_heads_scratch_doubles(plan, stride). */
+size_t mfgm_cq_heads_scratch_doubles(const mfgm_plan* plan, int stride);   /* 0: the plan or the stride does not qualify */
+int mfgm_cq_factor_pair_heads(const mfgm_plan* plan, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y,
+                              double* logdet, double* quad, double* L2, double* y2, double* scratch, size_t scratch_doubles, void* ws, int* info,
+                              void* stream);
+/* one part of it alone (profiling): the stages of mfgm_cq_factor_pair_stage, stage 0 being the shared reduce and the two tails */
+int mfgm_cq_factor_pair_heads_stage(const mfgm_plan* plan, int stage, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next,
+                                    double* L, double* y, double* L2, double* y2, double* scratch, size_t scratch_doubles, void* ws, int* info,
+                                    void* stream);
 /* mfgm_cq_selinv_girsanov on the second factorisation of mfgm_cq_factor_pair: the separator marginals come from the second copy of
  * the coarse levels (only_level 0: as the pair call left them; < 0: their backward pass is run again first). */
 int mfgm_cq_selinv_girsanov_alt(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L2, const double* y2,

@@ -19,6 +19,13 @@ void inst_pair(SweepArgs a, CqArgs q) {
     hipLaunchKernelGGL((k_forward_pair_cq<D>), dim3(1), dim3(128), 0, 0, a, q, a, q);
     hipLaunchKernelGGL((k_forward_pair_cq<D, 1>), dim3(1), dim3(128), 0, 0, a, q, a, q);
 }
+// the reduce of mfgm_cq_factor_pair_heads: the shared part and the tail, at the headline size and the largest one
+template <int D>
+void inst_heads(SweepArgs a, CqArgs q, double* park) {
+    hipLaunchKernelGGL((k_reduce_cq_interior<D>), dim3(1), dim3(64), 0, 0, a, q, park, 2);
+    hipLaunchKernelGGL((k_reduce_cq_heads<D>), dim3(1, 2), dim3(64), 0, 0, a, q, a, q, park, 2);
+}
+void inst_heads_all(SweepArgs a, CqArgs q, double* park) { inst_heads<6>(a, q, park); inst_heads<8>(a, q, park); }
 void inst_pairs(SweepArgs a, CqArgs q) {
     inst_pair<1>(a, q); inst_pair<2>(a, q); inst_pair<3>(a, q); inst_pair<4>(a, q); inst_pair<5>(a, q); inst_pair<6>(a, q);
 }

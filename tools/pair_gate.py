@@ -61,6 +61,15 @@ def main():
         assert lib.mfgm_cq_factor_pair_stage(pl.h, st, ctypes.byref(cst), ctypes.byref(nxt), _ptr(f["L"]), _ptr(f["y"]), _ptr(f2["L"]),
                                              _ptr(f2["y"]), _ptr(pl.ws), _ptr(pl.info), _stream()) == 0
 
+    # stage 0 of mfgm_cq_factor_pair_heads (one shared reduce + the two tails) where the model's observations allow it
+    stride = m._pair_head_stride()
+    scratch = pl._heads_scratch(stride) if stride else None
+
+    def heads(st):
+        assert lib.mfgm_cq_factor_pair_heads_stage(pl.h, st, stride, ctypes.byref(cst), ctypes.byref(nxt), _ptr(f["L"]), _ptr(f["y"]),
+                                                   _ptr(f2["L"]), _ptr(f2["y"]), _ptr(scratch), scratch.numel(), _ptr(pl.ws), _ptr(pl.info),
+                                                   _stream()) == 0
+
     klbuf = torch.empty(B, dtype=torch.float64, device=dev)
 
     def coarse_down():
@@ -75,11 +84,13 @@ def main():
             "coarse_up_single_ms": timed(lambda: single(2)), "coarse_up_pair_ms": timed(lambda: pair(2)),
             "coarse_down_single_ms": timed(coarse_down), "coarse_down_pair_ms": timed(lambda: pair(3)),
         }
+        if stride:
+            r["reduce_heads_ms"] = timed(lambda: heads(0))
         r["pair_over_two_forwards"] = r["forward_pair_ms"] / (2.0 * r["forward_alone_ms"])
     pl.check_info()
     out["gate"] = "forward pair <= 0.89 x two lone forward sweeps"
     out["passes"] = bool(max(out[k]["pair_over_two_forwards"] for k in ("round1", "round2")) <= 0.89)
-    out["config"] = dict(B=B, T=T, d=d, reps=a.reps, build=lib.mfgm_version().decode())
+    out["config"] = dict(B=B, T=T, d=d, reps=a.reps, head_stride=stride, build=lib.mfgm_version().decode())
     print(json.dumps(out))
 
 

@@ -398,7 +398,8 @@ int cq_factor_impl(const Plan& P0, const CqArgs& q, double* Lg, double* yg, doub
 // the separator marginals of their factorisation in place.  Every body is the one the single route runs: same numbers.
 template <int D>
 int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double* Lg, double* yg, double* logdet, double* quad, double* L2,
-                        double* y2, double* ws, int* info, hipStream_t st, int only_stage = -1) {
+                        double* y2, double* ws, int* info, hipStream_t st, int only_stage = -1, double* park = nullptr, int stride = 0) {
+    // park (mfgm_cq_factor_pair_heads): the two level-0 reduces share the elimination of everything but the observed nodes
     // only_stage (profiling): 0 the two level-0 reduces, 1 the level-0 forward pair, 2 the joint up phase of the levels above, 3 their
     // joint backward pass
     const auto on = [&](int s) { return only_stage < 0 || only_stage == s; };
@@ -417,7 +418,12 @@ int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double
     bind_up(P, 0, ws, a0);
     bind_up(P, 0, ws2, a1);
     dim3 grid(a0.lv.Lpad / 64), block(64);
-    if (on(0)) {
+    if (on(0) && park) {
+        hipLaunchKernelGGL((k_reduce_cq_interior<D>), grid, block, 0, st, a0, q, park, stride);
+        MFGM_CHECK_LAUNCH();
+        hipLaunchKernelGGL((k_reduce_cq_heads<D>), dim3(grid.x, 2), block, 0, st, a0, q, a1, q2, park, stride);
+        MFGM_CHECK_LAUNCH();
+    } else if (on(0)) {
         hipLaunchKernelGGL((k_reduce_cq<D>), grid, block, 0, st, a0, q);
         MFGM_CHECK_LAUNCH();
         hipLaunchKernelGGL((k_reduce_cq<D>), grid, block, 0, st, a1, q2);
@@ -790,6 +796,43 @@ int mfgm_cq_factor_pair_stage(const mfgm_plan* plan, int stage, const mfgm_cq_st
     const Plan& P = plan->p;
     const CqArgs c = cq_args(q), c2 = cq_args(q_next);
     MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, nullptr, nullptr, L2, y2, (double*)ws, info, (hipStream_t)stream, stage)));
+}
+
+size_t mfgm_cq_heads_scratch_doubles(const mfgm_plan* plan, int stride) {
+    if (!plan || plan->p.wide || stride < 2 || plan->p.lv[0].R % stride != 0) return 0;
+    const Plan& P = plan->p;
+    const size_t ET = (size_t)P.d * (P.d + 1) / 2, E = 2 * ET + 2 * P.d + (size_t)P.d * P.d;
+    return (size_t)P.lv[0].Lpad * (P.lv[0].R / stride) * E;
+}
+
+static bool cq_pair_heads_ok(const mfgm_plan* plan, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next, const double* L,
+                             const double* y, const double* L2, const double* y2, const double* scratch, size_t scratch_doubles, const void* ws,
+                             const int* info) {
+    if (!cq_ok(plan, q) || !cq_ok(plan, q_next) || !L || !y || !L2 || !y2 || L2 == L || y2 == y || !scratch || !ws || !info) return false;
+    if (stride < 2 || plan->p.lv[0].R % stride != 0 || plan->p.off_pair == 0) return false;
+    if (scratch_doubles < mfgm_cq_heads_scratch_doubles(plan, stride)) return false;      // (the parked stores would leave the array)
+    return q_next->dyn == q->dyn && q_next->slot == q->slot && q_next->p0_off == q->p0_off && q_next->d_off == q->d_off &&
+           q_next->s_off == q->s_off;
+}
+
+int mfgm_cq_factor_pair_heads(const mfgm_plan* plan, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y,
+                              double* logdet, double* quad, double* L2, double* y2, double* scratch, size_t scratch_doubles, void* ws, int* info,
+                              void* stream) {
+    if (!cq_pair_heads_ok(plan, stride, q, q_next, L, y, L2, y2, scratch, scratch_doubles, ws, info)) return 1;
+    const Plan& P = plan->p;
+    const CqArgs c = cq_args(q), c2 = cq_args(q_next);
+    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, logdet, quad, L2, y2, (double*)ws, info, (hipStream_t)stream, -1, scratch,
+                                                  stride)));
+}
+
+int mfgm_cq_factor_pair_heads_stage(const mfgm_plan* plan, int stage, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next,
+                                    double* L, double* y, double* L2, double* y2, double* scratch, size_t scratch_doubles, void* ws, int* info,
+                                    void* stream) {
+    if (!cq_pair_heads_ok(plan, stride, q, q_next, L, y, L2, y2, scratch, scratch_doubles, ws, info) || stage < 0 || stage > 3) return 1;
+    const Plan& P = plan->p;
+    const CqArgs c = cq_args(q), c2 = cq_args(q_next);
+    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, nullptr, nullptr, L2, y2, (double*)ws, info, (hipStream_t)stream, stage,
+                                                  scratch, stride)));
 }
 
 int mfgm_cq_selinv_girsanov_alt(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L2, const double* y2,

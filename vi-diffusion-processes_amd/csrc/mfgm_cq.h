@@ -197,6 +197,8 @@ MFGM_DEV void reduce_cq_body(const SweepArgs& a, const CqArgs& q, double* lds_ac
                 if (sites) sn = cq_slot(q.slot, R, s + 2, me);
             }
             // eliminate interior node s
+            // (cq_elim_step below restates this step for k_reduce_cq_interior / k_reduce_cq_heads, the same calls in the same order:
+            //  an edit here belongs there too, or mfgm_cq_factor_pair_heads no longer rounds as mfgm_cq_factor does)
             double invd[D], G[EF];
             chol_inplace<D>(F, invd, bad);
             trsm_left_lower<D>(F, invd, W);        // W := L^{-1} W   (spike towards the left separator)
@@ -289,6 +291,272 @@ MFGM_DEV void reduce_cq_body(const SweepArgs& a, const CqArgs& q, double* lds_ac
     if (p > 0) {
         const int qq = p - 1, ul = b * uP + qq / uR, us = qq % uR;
         st_node<EF, true>(a.uS, uR, us, LaneRef::of(ul), W);      // couples separator p-1 -> p
+        st_node<ET, true>(a.uRsub, uR, us, LaneRef::of(ul), Racc);
+        st_node<D, true>(a.urho, uR, us, LaneRef::of(ul), rho);
+    }
+    if (bad) flag_not_pd(a.info, a.lv.level, lane);
+}
+
+// ---- the level-0 reduce of TWO site sets, observed nodes eliminated last (mfgm_cq_factor_pair_heads) -----------------------------------
+// The reduce forms the Schur complement of a segment's interior onto its separators, and any elimination order gives that
+// complement.  With observations only at local steps that are multiples of `stride` (R = m stride), the nodes at those steps ("heads")
+// and the segment's last node are kept to the end: what is eliminated before them -- the interiors between consecutive kept nodes -- sees
+// dyn and the offsets alone, so it is done ONCE for both factorisations of a pair (k_reduce_cq_interior) and parked; the <= m steps on
+// the kept nodes, the only ones the sites enter, are made per site set (k_reduce_cq_heads).
+// Parked per sub-segment k (kept nodes lo = k stride, hi = min(lo + stride, len - 1)), [tile][k][element][64 lanes]: the diagonal block
+// F' and right-hand side h' of node hi after the interior is gone, the spike V that couples hi to lo, and what lo's block and
+// right-hand side lose, Racc and rho.  An empty interior parks (A_hi, r_hi, B_lo, 0, 0).
+template <int D>
+struct CqPark {
+    static constexpr int ET = MFGM_NTRI(D), EF = D * D;
+    static constexpr int F = 0, H = ET, V = ET + D, RACC = ET + D + EF, RHO = 2 * ET + D + EF, E = 2 * ET + 2 * D + EF;
+};
+template <int N>
+MFGM_DEV void park_st(double* __restrict__ p, const double (&v)[N]) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) p[e * 64] = v[e];
+}
+template <int N>
+MFGM_DEV void park_ld(const double* __restrict__ p, double (&v)[N]) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = p[e * 64];
+}
+// One elimination step of reduce_cq_body<D, false>, the same calls in the same order (that body is left as it is so that every
+// kernel built on it keeps its code; the two copies are edited together).  On entry F / h are the node's diagonal block and
+// right-hand side, W its spike towards the left separator and G its coupling to the next kept node.  On exit Racc += W'^T W' and
+// rho += W'^T y with W' = L^{-1} W, y = L^{-1} h; F = G' G'^T and t = G' y with G' = G L^{-T} are what the next node's block and
+// right-hand side lose; W = -G' W' is the spike from the next node.
+template <int D>
+MFGM_DEV void cq_elim_step(double (&F)[MFGM_NTRI(D)], double (&W)[D * D], double (&h)[D], double (&Racc)[MFGM_NTRI(D)], double (&rho)[D],
+                           double (&G)[D * D], double (&t)[D], int& bad) {
+    double invd[D];
+    chol_inplace<D>(F, invd, bad);
+    trsm_left_lower<D>(F, invd, W);
+    syrk_t_acc<D>(W, Racc);
+    {
+        trsv_lower<D>(F, invd, h);
+        double u[D];
+        gemv_t<D>(W, h, u);
+#pragma unroll
+        for (int e = 0; e < D; ++e) rho[e] += u[e];
+    }
+    trsm_right_lower_t<D>(F, invd, G);
+    syrk_set<D>(G, F);
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        double col[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) col[k] = W[k * D + c];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) s = __builtin_fma(G[i * D + k], col[k], s);
+            W[i * D + c] = -s;
+        }
+    }
+    gemv<D>(G, h, t);
+}
+
+// The shared part: one lane per segment walks its records once, as k_reduce_cq does (the record of node s + 2 requested a step ahead),
+// reads no slot and no site.  At a head the recurrence starts again with that head in the role of the left separator; when the next
+// node is a kept one the sub-segment is parked.
+template <int D>
+static __global__ __launch_bounds__(64) void k_reduce_cq_interior(SweepArgs a, CqArgs q, double* __restrict__ park, int stride) {
+    constexpr int ET = MFGM_NTRI(D), EF = D * D, E3 = 3 * D;
+    using PK = CqPark<D>;
+    const int lane = blockIdx.x * 64 + threadIdx.x;
+    if (lane >= a.lv.L) return;
+    const LaneRef me{(int)blockIdx.x, (int)threadIdx.x};
+    const int P = a.lv.P, R = a.lv.R;
+    const int b = lane / P, p = lane - b * P;
+    const int len = min(R, a.lv.n - p * R);
+    double* pk = park + (size_t)me.tile * (R / stride) * (PK::E * 64) + me.l;      // sub-segment 0 of this lane
+    int bad = 0;
+
+    double F[ET], W[EF], h[D], Racc[ET], rho[D], sdc[D], rn[E3];
+    if (len > 1) {
+        ld_part<E3, 2 * D, D>(q.dyn, R, 0, me, sdc);
+        ld_node<E3>(q.dyn, R, 1, me, rn);
+    }
+    int c = 0;                                       // s mod stride: node s is a head when it is 0
+    for (int s = 0; s < R - 1; ++s) {
+        if (s < len - 1) {
+            double rc[E3];
+#pragma unroll
+            for (int e = 0; e < E3; ++e) rc[e] = rn[e];
+            if (s + 1 < len - 1) ld_node<E3>(q.dyn, R, s + 2, me, rn);
+            if (c == 0) {
+                // node s is kept: node s + 1 opens the next interior (or is the next kept node: an empty interior)
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) F[tix(i, j)] = a.aD * ((i == j) ? rc[D + i] : q.dOff);
+#pragma unroll
+                for (int i = 0; i < D; ++i) h[i] = a.aR * rc[i];
+                cq_sub<D>(sdc, q.sOff, W);
+#pragma unroll
+                for (int e = 0; e < EF; ++e) W[e] *= a.aS;
+#pragma unroll
+                for (int e = 0; e < ET; ++e) Racc[e] = 0.0;
+#pragma unroll
+                for (int e = 0; e < D; ++e) rho[e] = 0.0;
+            } else {
+                double G[EF], t[D];
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j < D; ++j) G[i * D + j] = a.aS * ((i == j) ? sdc[i] : q.sOff);
+                cq_elim_step<D>(F, W, h, Racc, rho, G, t, bad);
+#pragma unroll
+                for (int i = 0; i < D; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) F[tix(i, j)] = __builtin_fma(a.aD, (i == j) ? rc[D + i] : q.dOff, -F[tix(i, j)]);
+#pragma unroll
+                for (int e = 0; e < D; ++e) h[e] = __builtin_fma(a.aR, rc[e], -t[e]);
+            }
+#pragma unroll
+            for (int i = 0; i < D; ++i) sdc[i] = rc[2 * D + i];
+            if (c == stride - 1 || s + 1 == len - 1) {
+                park_st<ET>(pk + PK::F * 64, F);
+                park_st<D>(pk + PK::H * 64, h);
+                park_st<EF>(pk + PK::V * 64, W);
+                park_st<ET>(pk + PK::RACC * 64, Racc);
+                park_st<D>(pk + PK::RHO * 64, rho);
+            }
+        }
+        if (++c == stride) {
+            c = 0;
+            pk += PK::E * 64;
+        }
+    }
+    if (bad) flag_not_pd(a.info, a.lv.level, lane);
+}
+
+// The tail, per site set (blockIdx.y: 0 -> (a, q), 1 -> (a2, q2); the two differ in the site arrays and in the copy of level 1 they
+// write): head 0 with its site, p0off and what its interior took; then one step per sub-segment with the parked spike in the place of
+// theta_sub, the next kept node taking its parked block, its own site and -- a head with an interior of its own -- what that interior
+// took.  Ends as reduce_cq_body does.
+template <int D>
+static __global__ __launch_bounds__(64) void k_reduce_cq_heads(SweepArgs a, CqArgs q, SweepArgs a2, CqArgs q2, const double* __restrict__ park,
+                                                               int stride) {
+    constexpr int ET = MFGM_NTRI(D), EF = D * D, E3 = 3 * D;
+    using PK = CqPark<D>;
+    const int lane = blockIdx.x * 64 + threadIdx.x;
+    if (lane >= a.lv.L) return;
+    const bool second = (blockIdx.y != 0);
+    if (second) {
+        q.site_lin = q2.site_lin; q.site_sym = q2.site_sym;
+        a.uDhat = a2.uDhat; a.urhat = a2.urhat; a.uRsub = a2.uRsub; a.urho = a2.urho; a.uS = a2.uS;
+    }
+    const LaneRef me{(int)blockIdx.x, (int)threadIdx.x};
+    const int P = a.lv.P, R = a.lv.R;
+    const int b = lane / P, p = lane - b * P;
+    const int len = min(R, a.lv.n - p * R);
+    const int m = R / stride, nsub = (len + stride - 2) / stride;
+    const double* pk = park + (size_t)me.tile * m * (PK::E * 64) + me.l;
+    const bool sites = (q.slot != nullptr);
+    int bad = 0;
+    double ssym[ET];
+    cq_site_sym<ET>(q, sites, ssym);
+
+    double F[ET], W[EF], h[D], Racc[ET], rho[D];
+    {
+        double r0[E3];
+        ld_node<E3>(q.dyn, R, 0, me, r0);
+        const int s0 = sites ? cq_slot(q.slot, R, 0, me) : -1;
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) F[tix(i, j)] = (i == j) ? r0[D + i] : q.dOff;
+#pragma unroll
+        for (int i = 0; i < D; ++i) h[i] = r0[i];
+        if (s0 >= 0) {
+#pragma unroll
+            for (int e = 0; e < ET; ++e) F[e] += ssym[e];
+#pragma unroll
+            for (int i = 0; i < D; ++i) h[i] += q.site_lin[(size_t)s0 * D + i];
+        }
+        if (p == 0 && q.p0off) {
+#pragma unroll
+            for (int e = 0; e < ET; ++e) F[e] += q.p0off[e];
+        }
+#pragma unroll
+        for (int e = 0; e < ET; ++e) F[e] *= a.aD;
+#pragma unroll
+        for (int i = 0; i < D; ++i) h[i] *= a.aR;
+        if (nsub > 0) {
+            park_ld<ET>(pk + PK::RACC * 64, Racc);
+            park_ld<D>(pk + PK::RHO * 64, rho);
+#pragma unroll
+            for (int e = 0; e < ET; ++e) F[e] -= Racc[e];
+#pragma unroll
+            for (int i = 0; i < D; ++i) h[i] -= rho[i];
+        }
+    }
+    if (p > 0) {
+        double sl_[D];
+        ld_part<E3, 2 * D, D>(q.dyn, R, R - 1, LaneRef::of(lane - 1), sl_);
+        cq_sub<D>(sl_, q.sOff, W);
+#pragma unroll
+        for (int e = 0; e < EF; ++e) W[e] *= a.aS;
+    } else {
+#pragma unroll
+        for (int e = 0; e < EF; ++e) W[e] = 0.0;
+    }
+#pragma unroll
+    for (int e = 0; e < ET; ++e) Racc[e] = 0.0;
+#pragma unroll
+    for (int e = 0; e < D; ++e) rho[e] = 0.0;
+
+    for (int k = 0; k < m; ++k) {
+        if (k < nsub) {
+            const int hi = (k + 1) * stride;             // the next kept node is this head, or the last node when that comes first
+            double G[EF], t[D], sl[D];
+            park_ld<EF>(pk + PK::V * 64, G);
+            const int sc = (sites && hi <= len - 1) ? cq_slot(q.slot, R, hi, me) : -1;
+#pragma unroll
+            for (int i = 0; i < D; ++i) sl[i] = 0.0;
+            if (sc >= 0) {
+#pragma unroll
+                for (int i = 0; i < D; ++i) sl[i] = q.site_lin[(size_t)sc * D + i];
+            }
+            cq_elim_step<D>(F, W, h, Racc, rho, G, t, bad);
+            double Fp[ET], hp[D];
+            park_ld<ET>(pk + PK::F * 64, Fp);
+            park_ld<D>(pk + PK::H * 64, hp);
+            const double cnt = (sc >= 0) ? a.aD : 0.0;
+#pragma unroll
+            for (int e = 0; e < ET; ++e) F[e] = __builtin_fma(cnt, ssym[e], Fp[e]) - F[e];
+#pragma unroll
+            for (int e = 0; e < D; ++e) h[e] = __builtin_fma(a.aR, sl[e], hp[e]) - t[e];
+            pk += PK::E * 64;
+            if (k + 1 < nsub) {
+                // that head has an interior of its own to the right
+                park_ld<ET>(pk + PK::RACC * 64, Fp);
+                park_ld<D>(pk + PK::RHO * 64, hp);
+#pragma unroll
+                for (int e = 0; e < ET; ++e) F[e] -= Fp[e];
+#pragma unroll
+                for (int e = 0; e < D; ++e) h[e] -= hp[e];
+            }
+        }
+    }
+    // as reduce_cq_body: the separator of this segment is node p of the coarser level
+    const int uP = a.up.P, uR = a.up.R;
+    {
+        const int qq = p, ul = b * uP + qq / uR, us = qq % uR;
+        st_node<ET, true>(a.uDhat, uR, us, LaneRef::of(ul), F);
+        st_node<D, true>(a.urhat, uR, us, LaneRef::of(ul), h);
+        if (p == P - 1) {
+            st_node_zero<ET, true>(a.uRsub, uR, us, LaneRef::of(ul));
+            st_node_zero<D, true>(a.urho, uR, us, LaneRef::of(ul));
+            st_node_zero<EF, true>(a.uS, uR, us, LaneRef::of(ul));
+        }
+    }
+    if (p > 0) {
+        const int qq = p - 1, ul = b * uP + qq / uR, us = qq % uR;
+        st_node<EF, true>(a.uS, uR, us, LaneRef::of(ul), W);
         st_node<ET, true>(a.uRsub, uR, us, LaneRef::of(ul), Racc);
         st_node<D, true>(a.urho, uR, us, LaneRef::of(ul), rho);
     }

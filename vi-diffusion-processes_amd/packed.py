@@ -497,11 +497,14 @@ class Plan:
                    "mfgm_cq_factor_pipelined")
         return dict(L=L, y=y, logdet=logdet)
 
-    def cq_factor_pair(self, cq, next_sites, out=None, out2=None, want_logdet=True):
+    def cq_factor_pair(self, cq, next_sites, out=None, out2=None, want_logdet=True, head_stride=None):
         """Two factorisations of one dyn in one call (mfgm_cq_factor_pair): that of `cq` -> dict(L, y, logdet) and that of the same
         state with the observation sites `next_sites` = (site_lin, site_sym) -> the second dict(L, y).  The levels above the finest one
         run once at double width; both coarse backward passes are made, so the sweeps that follow take only_level=0:
-        cq_selinv_kl on the first, cq_selinv_girsanov(alt=True) on the second."""
+        cq_selinv_kl on the first, cq_selinv_girsanov(alt=True) on the second.
+        head_stride: every observation sits at a local step of its segment that is a multiple of it (the caller's word); the level-0
+        reduces then share the elimination of everything but the observed nodes (mfgm_cq_factor_pair_heads; the plan keeps the
+        scratch array)."""
         out = {} if out is None else out
         out2 = {} if out2 is None else out2
         L = out.get("L") if out.get("L") is not None else self.empty(TRI)
@@ -512,9 +515,24 @@ class Plan:
         logdet = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
         nxt = cq.struct()
         nxt.site_lin, nxt.site_sym = next_sites[0].data_ptr(), next_sites[1].data_ptr()
+        if head_stride is not None:
+            scratch = self._heads_scratch(int(head_stride))
+            _lib.check(self.lib.mfgm_cq_factor_pair_heads(self.h, int(head_stride), ctypes.byref(cq.struct()), ctypes.byref(nxt), _ptr(L), _ptr(y),
+                                                          _ptr(logdet), None, _ptr(L2), _ptr(y2), _ptr(scratch), scratch.numel(), _ptr(self.ws),
+                                                          _ptr(self.info), _stream()), "mfgm_cq_factor_pair_heads")
+            return dict(L=L, y=y, logdet=logdet), dict(L=L2, y=y2)
         _lib.check(self.lib.mfgm_cq_factor_pair(self.h, ctypes.byref(cq.struct()), ctypes.byref(nxt), _ptr(L), _ptr(y), _ptr(logdet), None,
                                                 _ptr(L2), _ptr(y2), _ptr(self.ws), _ptr(self.info), _stream()), "mfgm_cq_factor_pair")
         return dict(L=L, y=y, logdet=logdet), dict(L=L2, y=y2)
+
+    def _heads_scratch(self, stride):
+        """The array mfgm_cq_factor_pair_heads parks its shared part in, kept from call to call (one stride per plan in practice).
+        A stride the library refuses gets a one-element array: the call itself reports the argument error."""
+        held = getattr(self, "_heads_buf", None)
+        if held is None or held[0] != stride:
+            n = self.lib.mfgm_cq_heads_scratch_doubles(self.h, stride)
+            held = self._heads_buf = (stride, torch.empty(max(int(n), 1), dtype=torch.float64, device=self.device))
+        return held[1]
 
     def cq_selinv_girsanov(self, cq, L, y, prm, dyn_out, only_level=-1, alt=False):
         """alt: (L, y) is the second factorisation of cq_factor_pair (its coarse levels are the workspace's second copy)."""

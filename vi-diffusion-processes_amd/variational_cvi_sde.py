@@ -74,6 +74,10 @@ class CVISitesSSM:
             plan = prior_ssm.plan if prior_ssm is not None else Plan(self.B, self.T, self.state_dim, R0=r0, device=self.device)
         self.plan = plan
         self.obs_node_ids = plan.node_ids(self.obs_sites_indices)
+        # equally spaced observations whose indices are multiples of the spacing: that spacing (0: none).  With a segment length that
+        # is a multiple of it too, every observation sits at a local step that is one (Plan.cq_factor_pair(head_stride=...))
+        q = observation_period(self.obs_sites_indices)
+        self._obs_stride = q if q >= 2 and bool((self.obs_sites_indices % q == 0).all()) else 0
         d, pl = self.state_dim, plan
         # Girsanov sites start at nat1 = 0, nat2 = -1e-10 * ones (variational_cvi_sde.py:141-152).  They are not stored:
         # theta_q = theta_prior + girsanov + scatter(data) is the resident state and the sites are recovered from it on
@@ -684,9 +688,19 @@ class CVISitesSDE(CVISitesSSM):
     # which the level-0 SIMDs idle -- run once per step at double width instead of twice, and the two level-0 forward sweeps share one
     # read of the records.  One more factor buffer (L, y) is held.  0: the level-0 reduce alone is made ahead, as above.
     pipe_pair = os.environ.get("VIDP_PIPE_PAIR", "1") != "0"
+    # VIDP_PAIR_HEADS=0: the pair's two level-0 reduces each eliminate their whole segments (mfgm_cq_factor_pair) even where the
+    # observations sit on a regular grid through the origin and the segment length is a multiple of its spacing; by default such a
+    # model eliminates the unobserved nodes once for both (mfgm_cq_factor_pair_heads; A/B in DESIGN.md 5d)
+    pair_heads = os.environ.get("VIDP_PAIR_HEADS", "1") != "0"
     # below this many nodes (B T) a level-0 reduce is a few microseconds: the second stream's event round trips would cost more than
     # they hide (config 1, T = 1001: 0.133 -> 0.174 ms with it)
     pipeline_min_nodes = 200000
+
+    def _pair_head_stride(self):
+        """The stride Plan.cq_factor_pair shares its level-0 reduces on, or None: the observation spacing when every observation
+        index and the level-0 segment length are multiples of it."""
+        q = self._obs_stride
+        return q if self.pair_heads and q >= 2 and self.plan.R % q == 0 else None
 
     def _site_blend(self, cq, lin, sym, lr):
         """(lin, sym) <- (1 - lr) site + lr gradient (variational_cvi_sde.py:301-317), both site arrays in one launch."""
@@ -773,7 +787,8 @@ class CVISitesSDE(CVISitesSSM):
                     self._site_blend(cq, lin, sym, lr_next)
                     if pair:
                         # the WHOLE first factorisation of the next step with this one: the coarse levels of both in one chain
-                        f, f2 = pl.cq_factor_pair(cq, (lin, sym), out=self._bufs["f"], out2=self._bufs.setdefault("f2", {}))
+                        f, f2 = pl.cq_factor_pair(cq, (lin, sym), out=self._bufs["f"], out2=self._bufs.setdefault("f2", {}),
+                                                  head_stride=self._pair_head_stride())
                         self._bufs["f2"].update(L=f2["L"], y=f2["y"])
                         return f, f2
                     return pl.cq_factor(cq, want_logdet=True, out=self._bufs["f"], next_sites=(lin, sym), side=ahead.side)
