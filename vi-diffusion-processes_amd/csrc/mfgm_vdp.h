@@ -452,10 +452,7 @@ __global__ __launch_bounds__(64) void k_vdp_marginals(LevelDesc lv, VdpParams pr
                             } else {
                                 ld_node<ET>(dobsS, R, s, me, dob);
                             }
-                            if (pr.clip > 0.0) {
-#pragma unroll
-                                for (int e = 0; e < ET; ++e) dob[e] = vdp_stab(dob[e], pr.clip);
-                            }
+                            // d_obs_m = yR + 2 dobsS m from the block as it is: the reference clips d_obs_m and d_obs_S each on its own
 #pragma unroll
                             for (int i = 0; i < D; ++i) {
                                 double dom = yr[i];
@@ -465,7 +462,7 @@ __global__ __launch_bounds__(64) void k_vdp_marginals(LevelDesc lv, VdpParams pr
                                 dm[i] -= dom;
                             }
 #pragma unroll
-                            for (int e = 0; e < ET; ++e) dS[e] -= dob[e];
+                            for (int e = 0; e < ET; ++e) dS[e] -= pr.clip > 0.0 ? vdp_stab(dob[e], pr.clip) : dob[e];
                         }
                         // Cpsi += c Mp, then Mp <- (I - 2 dt A) Mp, a column at a time
 #pragma unroll
@@ -919,6 +916,15 @@ __global__ __launch_bounds__(64) void k_vdp_lagrange(LevelDesc lv, VdpParams pr,
                         ld_node<ET>(dobsS, R, s, me, dob);
                     }
                     vdp_energy<D, true>(pr, m, S, A, bb, dm, dS);
+                    // d_obs_m = yR + 2 dobsS m (kept in yr) from the block as it is: the reference clips d_obs_m and d_obs_S each on its own
+                    // (vi_sde.py:312-323), so the block is clipped only after this
+#pragma unroll
+                    for (int i = 0; i < D; ++i) {
+                        double dom = yr[i];
+#pragma unroll
+                        for (int k = 0; k < D; ++k) dom = __builtin_fma(2.0 * dob[six(i, k)], m[k], dom);
+                        yr[i] = dom;
+                    }
                     if (pr.clip > 0.0) {        // vi_sde.py:312-323
 #pragma unroll
                         for (int i = 0; i < D; ++i) dm[i] = vdp_stab(dm[i], pr.clip);
@@ -931,10 +937,7 @@ __global__ __launch_bounds__(64) void k_vdp_lagrange(LevelDesc lv, VdpParams pr,
                     gemv<D>(A, lam, al);
 #pragma unroll
                     for (int i = 0; i < D; ++i) {
-                        double dom = yr[i];
-#pragma unroll
-                        for (int k = 0; k < D; ++k) dom = __builtin_fma(2.0 * dob[six(i, k)], m[k], dom);
-                        if (pr.clip > 0.0) dom = vdp_stab(dom, pr.clip);
+                        const double dom = pr.clip > 0.0 ? vdp_stab(yr[i], pr.clip) : yr[i];
                         lam[i] = lam[i] - pr.dt * (al[i] - dm[i]) - dom;
 #pragma unroll
                         for (int j = 0; j < D; ++j)
