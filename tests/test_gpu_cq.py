@@ -17,8 +17,8 @@ Kernel instantiations and the test that launches them (D = 1 ... 8 unless noted)
   k_mvn_ve_compact<D>, k_cq_elbo (mfgm_cq_elbo), k_sum_partials    test_cq_factor_and_kl_sweep
   k_backward_girsanov_cq<D, 0>, k_girsanov_fixup_cq<D>             test_cq_girsanov_sweep
   k_cq_pack<D>, k_cq_unpack<D>, k_cq_slots                         test_cq_equals_dense_entry_points (k_cq_slots: every test)
-  k_forward_reduce_cq<D, 0> (D = 1 ... 6 only: the dispatch never
-  launches it at D = 7, 8)                                         test_cq_pipelined_forms, one stream
+  k_forward_reduce_cq<D, 0> (D = 1 ... 6 only: it is not
+  instantiated at D = 7, 8, nor is <D, 1>)                         test_cq_pipelined_forms, one stream
   k_reduce_cq_lean<D>                                              test_cq_pipelined_forms: side stream at every D; same stream at D = 7, 8
   k_forward_cq<D, 2>, k_backward_girsanov_cq<D, 2>,
   k_backward_kl_cq<D, 2>            D = 1, 3, 6, 8                 test_cq_cache_policy_variants (MFGM_NT=2)

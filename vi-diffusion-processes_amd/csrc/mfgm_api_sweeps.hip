@@ -106,12 +106,102 @@ int coarse_rows_p() {
     return std::max(0, std::min(atoi(e), kRowsMaxP));
 }
 
+// ---- the levels above the finest one -----------------------------------------------------------------------------------------------
+// Every driver below is: level-0 reduce, coarse_up, level-0 forward and, for a selected inverse, coarse_down, level-0 backward.  The
+// walk over the levels >= 1 lives here alone: one launch per level and pass below coarse_fuse_from(P), one fused launch from there to
+// the top.  The staged (profiling) calls launch one level through the same *_level helpers.
 template <int D>
-int launch_coarse_backward(const Plan& P, int lf, bool has_rhs, double* ws, hipStream_t st) {
-    if (has_rhs) hipLaunchKernelGGL((k_coarse_backward<D, true>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p());
-    else hipLaunchKernelGGL((k_coarse_backward<D, false>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p());
+int reduce_level(const Plan& P, int l, double* ws, int* info, bool has_rhs, hipStream_t st) {
+    return launch_reduce<D>(coarse_level_args(P, l, ws, info), has_rhs, true, st);
+}
+template <int D>
+int forward_level(const Plan& P, int l, double* ws, int* info, bool has_rhs, hipStream_t st) {
+    return launch_forward<D>(coarse_level_args(P, l, ws, info), has_rhs, true, l < P.nlevels - 1, st);
+}
+template <int D>
+int backward_level(const Plan& P, int l, double* ws, bool has_rhs, hipStream_t st) {
+    return launch_backward<D>(coarse_level_args(P, l, ws, nullptr), has_rhs, l < P.nlevels - 1, false, st, true);
+}
+
+// levels >= 1 of a factorisation: reduce 1 .. lf-1, levels lf .. K in one launch (reduce lf .. K-1, forward K .. lf), forward lf-1 .. 1
+template <int D>
+int coarse_up(const Plan& P, double* ws, int* info, bool has_rhs, hipStream_t st) {
+    const int K = P.nlevels - 1, lf = coarse_fuse_from(P);
+    for (int l = 1; l < K && l < lf; ++l)
+        if (int rc = reduce_level<D>(P, l, ws, info, has_rhs, st)) return rc;
+    if (lf <= K) {
+        if (has_rhs) hipLaunchKernelGGL((k_coarse_factor<D, true>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p());
+        else hipLaunchKernelGGL((k_coarse_factor<D, false>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p());
+        MFGM_CHECK_LAUNCH();
+    }
+    for (int l = std::min(K, lf - 1); l >= 1; --l)
+        if (int rc = forward_level<D>(P, l, ws, info, has_rhs, st)) return rc;
+    return 0;
+}
+// levels >= 1 of a selected inverse: backward K .. lf in one launch, backward lf-1 .. 1
+template <int D>
+int coarse_down(const Plan& P, double* ws, bool has_rhs, hipStream_t st) {
+    const int K = P.nlevels - 1, lf = coarse_fuse_from(P);
+    if (lf <= K) {
+        if (has_rhs) hipLaunchKernelGGL((k_coarse_backward<D, true>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p());
+        else hipLaunchKernelGGL((k_coarse_backward<D, false>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p());
+        MFGM_CHECK_LAUNCH();
+    }
+    for (int l = std::min(K, lf - 1); l >= 1; --l)
+        if (int rc = backward_level<D>(P, l, ws, has_rhs, st)) return rc;
+    return 0;
+}
+// The same two walks for TWO factorisations at double width (mfgm_cq_factor_pair): the first in the levels >= 1 at `ws`, the second in
+// their copy at `ws + shift`.
+template <int D>
+int coarse_up_pair(const Plan& P, double* ws, size_t shift, int* info, hipStream_t st) {
+    const int K = P.nlevels - 1, lf = coarse_fuse_from(P);
+    for (int l = 1; l < K && l < lf; ++l) {
+        const SweepArgs a = coarse_level_args(P, l, ws, info), b = coarse_level_args(P, l, ws + shift, info);
+        hipLaunchKernelGGL((k_reduce_pair<D>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b);
+        MFGM_CHECK_LAUNCH();
+    }
+    if (lf <= K) {
+        hipLaunchKernelGGL((k_coarse_factor_pair<D, true>), dim3(2 * P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p(), shift);
+        MFGM_CHECK_LAUNCH();
+    }
+    for (int l = std::min(K, lf - 1); l >= 1; --l) {
+        const SweepArgs a = coarse_level_args(P, l, ws, info), b = coarse_level_args(P, l, ws + shift, info);
+        if (l < K) hipLaunchKernelGGL((k_forward_pair<D, true>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b);
+        else hipLaunchKernelGGL((k_forward_pair<D, false>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b);
+        MFGM_CHECK_LAUNCH();
+    }
+    return 0;
+}
+template <int D>
+int coarse_down_pair(const Plan& P, double* ws, size_t shift, hipStream_t st) {
+    const int K = P.nlevels - 1, lf = coarse_fuse_from(P);
+    if (lf <= K) {
+        hipLaunchKernelGGL((k_coarse_backward_pair<D, true>), dim3(2 * P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p(), shift);
+        MFGM_CHECK_LAUNCH();
+    }
+    for (int l = std::min(K, lf - 1); l >= 1; --l) {
+        const SweepArgs a = coarse_level_args(P, l, ws, nullptr), b = coarse_level_args(P, l, ws + shift, nullptr);
+        if (l < K) hipLaunchKernelGGL((k_backward_pair<D, true>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b);
+        else hipLaunchKernelGGL((k_backward_pair<D, false>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b);
+        MFGM_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// The per-chain sums of the level-0 partials in ONE k_sum_partials launch (second array at stride2; 0: there is none).  Not
+// launch_sum_partials, whose split form would add the same numbers in another order.
+int sum_level0_partials(const Plan& P, double* ws, int stride2, double* out0, double* out1, hipStream_t st) {
+    hipLaunchKernelGGL(k_sum_partials, dim3(P.B), dim3(256), 0, st, ws + P.off_part[0], P.lv[0].P, stride2, out0, out1);
     MFGM_CHECK_LAUNCH();
     return 0;
+}
+
+SdeParams sde_params(const mfgm_sde_params* prm) {
+    static_assert(sizeof(mfgm_sde_params) == sizeof(mfgm::SdeParams), "public and internal SDE parameter structs must match");
+    SdeParams pr;
+    memcpy(&pr, prm, sizeof(pr));
+    return pr;
 }
 
 template <int D>
@@ -121,40 +211,23 @@ int factor_impl(const Plan& P, const double* Dg, const double* Sg, const double*
     // partials_only: the per-lane log|L| / |y|^2 partials are left in ws + off_part[0] for the caller to sum (kf_elbo_impl)
     const bool has_rhs = (rg != nullptr);
     const int K = P.nlevels - 1;  // top level index (single segment per chain)
-    auto make = [&](int l) {
-        SweepArgs a;
-        memset(&a, 0, sizeof(a));
-        a.lv = P.lv[l];
-        a.info = info;
-        if (l == 0) {
-            a.Dg = Dg; a.Sg = Sg; a.rg = rg; a.aD = aD; a.aS = aS; a.aR = aR;
-            a.Lg = Lg; a.Gg = Gg; a.yg = yg;
-            a.part = (logdet || quad || partials_only) ? ws + P.off_part[0] : nullptr;
-        } else {
-            bind_level_inputs(P, l, ws, a);
-        }
-        if (l < K) bind_up(P, l, ws, a);
-        return a;
-    };
-    // levels lf .. K in one launch (reduce lf .. K-1, forward K .. lf); single-kernel profiling calls keep one launch per level
-    const int lf = (only_stage >= 0) ? P.nlevels : coarse_fuse_from(P);
-    for (int l = 0; l < K && l < lf; ++l) {
-        if (only_stage >= 0 && !(only_stage == 0 && only_level == l)) continue;
-        SweepArgs a = make(l);
-        int rc = launch_reduce<D>(a, has_rhs, l > 0, st);
-        if (rc) return rc;
-    }
-    if (lf <= K) {
-        if (has_rhs) hipLaunchKernelGGL((k_coarse_factor<D, true>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p());
-        else hipLaunchKernelGGL((k_coarse_factor<D, false>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p());
-        MFGM_CHECK_LAUNCH();
-    }
-    for (int l = std::min(K, lf - 1); l >= 0; --l) {
-        if (only_stage >= 0 && !(only_stage == 1 && only_level == l)) continue;
-        SweepArgs a = make(l);
-        int rc = launch_forward<D>(a, has_rhs, l > 0, l < K, st);
-        if (rc) return rc;
-    }
+    // single-kernel profiling calls above the finest level: that level's reduce or forward alone, no fusing
+    if (only_stage == 0 && only_level > 0) return reduce_level<D>(P, only_level, ws, info, has_rhs, st);
+    if (only_stage == 1 && only_level > 0) return forward_level<D>(P, only_level, ws, info, has_rhs, st);
+    SweepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.lv = P.lv[0];
+    a.info = info;
+    a.Dg = Dg; a.Sg = Sg; a.rg = rg; a.aD = aD; a.aS = aS; a.aR = aR;
+    a.Lg = Lg; a.Gg = Gg; a.yg = yg;
+    a.part = (logdet || quad || partials_only) ? ws + P.off_part[0] : nullptr;
+    if (K > 0) bind_up(P, 0, ws, a);
+    if (K > 0 && only_stage <= 0)
+        if (int rc = launch_reduce<D>(a, has_rhs, false, st)) return rc;
+    if (only_stage < 0)
+        if (int rc = coarse_up<D>(P, ws, info, has_rhs, st)) return rc;
+    if (only_stage != 0)
+        if (int rc = launch_forward<D>(a, has_rhs, false, K > 0, st)) return rc;
     if (only_stage < 0 && (logdet || quad)) {
         if (launch_sum_partials(ws + P.off_part[0], P.lv[0].P, P.lv[0].Lpad, P.B, logdet, quad, P.B == 1 ? ws + P.off_part2 : nullptr, st))
             return 3;
@@ -168,51 +241,26 @@ int selinv_impl(const Plan& P, const double* Lg, const double* Gg, const double*
                 double aS = 1.0) {
     const bool has_rhs = (yg != nullptr);
     const int K = P.nlevels - 1;
-    const int lf = (only_level >= 0) ? P.nlevels : coarse_fuse_from(P);
-    if (lf <= K) {
-        int rc = launch_coarse_backward<D>(P, lf, has_rhs, ws, st);
-        if (rc) return rc;
-    }
-    for (int l = std::min(K, lf - 1); l >= 0; --l) {
-        if (only_level >= 0 && only_level != l) continue;
-        SweepArgs a;
-        memset(&a, 0, sizeof(a));
-        a.lv = P.lv[l];
-        if (l == 0) {
-            a.Lg = const_cast<double*>(Lg); a.Gg = const_cast<double*>(Gg); a.yg = const_cast<double*>(yg);
-            a.Sigg = Sig; a.Subg = Sub; a.mug = x; a.momg = mom;
-            a.Sg = Sg; a.aS = aS;          // non-null Sg: level 0 reads S instead of L_{t+1,t} (see k_backward, USE_S)
-        } else {
-            bind_level_inputs(P, l, ws, a);
-        }
-        if (l < K) bind_up(P, l, ws, a);
-        int rc = launch_backward<D>(a, has_rhs, l < K, l == 0 && Sub != nullptr, st, l > 0);
-        if (rc) return rc;
-    }
-    return 0;
+    if (only_level > 0) return backward_level<D>(P, only_level, ws, has_rhs, st);      // profiling: that level alone, no fusing
+    if (only_level < 0)
+        if (int rc = coarse_down<D>(P, ws, has_rhs, st)) return rc;
+    SweepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.lv = P.lv[0];
+    a.Lg = const_cast<double*>(Lg); a.Gg = const_cast<double*>(Gg); a.yg = const_cast<double*>(yg);
+    a.Sigg = Sig; a.Subg = Sub; a.mug = x; a.momg = mom;
+    a.Sg = Sg; a.aS = aS;          // non-null Sg: level 0 reads S instead of L_{t+1,t} (see k_backward, USE_S)
+    if (K > 0) bind_up(P, 0, ws, a);
+    return launch_backward<D>(a, has_rhs, K > 0, Sub != nullptr, st);
 }
 
 template <int D>
 int selinv_girsanov_impl(const Plan& P, const double* Lg, const double* Sg, double aS, const double* yg, const SdeParams& pr,
                          const GirsanovArgs& g, double* ws, hipStream_t st, int only_level) {
     // coarser levels exactly as in a plain selected inverse, then the fused level-0 sweep
-    const int K = P.nlevels - 1;
-    const int lf = (only_level >= 0) ? P.nlevels : coarse_fuse_from(P);
-    if (lf <= K) {
-        int rc = launch_coarse_backward<D>(P, lf, true, ws, st);
-        if (rc) return rc;
-    }
-    for (int l = std::min(K, lf - 1); l >= 1; --l) {
-        if (only_level >= 0 && only_level != l) continue;
-        SweepArgs a;
-        memset(&a, 0, sizeof(a));
-        a.lv = P.lv[l];
-        bind_level_inputs(P, l, ws, a);
-        if (l < K) bind_up(P, l, ws, a);
-        int rc = launch_backward<D>(a, true, l < K, false, st, true);
-        if (rc) return rc;
-    }
-    if (only_level > 0) return 0;
+    if (only_level > 0) return backward_level<D>(P, only_level, ws, true, st);
+    if (only_level < 0)
+        if (int rc = coarse_down<D>(P, ws, true, st)) return rc;
     SweepArgs a;
     memset(&a, 0, sizeof(a));
     a.lv = P.lv[0];
@@ -231,23 +279,9 @@ int selinv_girsanov_impl(const Plan& P, const double* Lg, const double* Sg, doub
 template <int D>
 int selinv_kl_impl(const Plan& P, const double* Lg, const double* Sg, double aS, const double* yg, const SdeParams& pr, double* Sig,
                    double* x, double* kl, double* ws, hipStream_t st, int only_level) {
-    const int K = P.nlevels - 1;
-    const int lf = (only_level >= 0) ? P.nlevels : coarse_fuse_from(P);
-    if (lf <= K) {
-        int rc = launch_coarse_backward<D>(P, lf, true, ws, st);
-        if (rc) return rc;
-    }
-    for (int l = std::min(K, lf - 1); l >= 1; --l) {
-        if (only_level >= 0 && only_level != l) continue;
-        SweepArgs a;
-        memset(&a, 0, sizeof(a));
-        a.lv = P.lv[l];
-        bind_level_inputs(P, l, ws, a);
-        if (l < K) bind_up(P, l, ws, a);
-        int rc = launch_backward<D>(a, true, l < K, false, st, true);
-        if (rc) return rc;
-    }
-    if (only_level > 0) return 0;
+    if (only_level > 0) return backward_level<D>(P, only_level, ws, true, st);
+    if (only_level < 0)
+        if (int rc = coarse_down<D>(P, ws, true, st)) return rc;
     SweepArgs a;
     memset(&a, 0, sizeof(a));
     a.lv = P.lv[0];
@@ -257,9 +291,7 @@ int selinv_kl_impl(const Plan& P, const double* Lg, const double* Sg, double aS,
     bind_up(P, 0, ws, a);
     hipLaunchKernelGGL((k_backward_kl<D>), dim3(a.lv.Lpad / 64), dim3(64), 0, st, a, pr);
     MFGM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_sum_partials, dim3(P.B), dim3(256), 0, st, a.part, a.lv.P, 0, kl, (double*)nullptr);
-    MFGM_CHECK_LAUNCH();
-    return 0;
+    return sum_level0_partials(P, ws, 0, kl, nullptr, st);
 }
 
 // ---- CVI-DP sweeps on the structured ("cq") state: level 0 from mfgm_cq.h, coarser levels as usual ------------------------------------
@@ -295,7 +327,6 @@ int cq_factor_impl(const Plan& P0, const CqArgs& q, double* Lg, double* yg, doub
                    hipStream_t st, int only_stage = -1, const CqPipe* pipe = nullptr) {
     const int region = (pipe && pipe->use_ahead) ? pipe->owner->ahead_region : 0;
     const Plan P = with_l1_region(P0, region);
-    const int K = P.nlevels - 1;
     SweepArgs a0;
     memset(&a0, 0, sizeof(a0));
     a0.lv = P.lv[0];
@@ -315,80 +346,52 @@ int cq_factor_impl(const Plan& P0, const CqArgs& q, double* Lg, double* yg, doub
         hipLaunchKernelGGL((k_reduce_cq<D>), grid, block, 0, st, a0, q);
         MFGM_CHECK_LAUNCH();
     }
-    if (only_stage < 0 || only_stage == 2) {         // stage 2 (profiling): the levels above the finest one alone
-        const int lf = coarse_fuse_from(P);
-        for (int l = 1; l < K && l < lf; ++l) {
-            SweepArgs a = coarse_level_args(P, l, ws, info);
-            int rc = launch_reduce<D>(a, true, true, st);
-            if (rc) return rc;
-        }
-        if (lf <= K) {
-            hipLaunchKernelGGL((k_coarse_factor<D, true>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p());
-            MFGM_CHECK_LAUNCH();
-        }
-        for (int l = std::min(K, lf - 1); l >= 1; --l) {
-            SweepArgs a = coarse_level_args(P, l, ws, info);
-            int rc = launch_forward<D>(a, true, true, l < K, st);
-            if (rc) return rc;
-        }
-    }
-    if (pipe && pipe->next && !pipe->side && D > 6) {
-        // d = 7, 8: the two-wavefront kernel does not fit 256 registers; without a side stream the reduce made ahead simply follows the
-        // forward sweep on this stream (correct, nothing overlapped)
-        SweepArgs an = a0;
+    if (only_stage < 0 || only_stage == 2)           // stage 2 (profiling): the levels above the finest one alone
+        if (int rc = coarse_up<D>(P, ws, info, true, st)) return rc;
+    // Level-0 forward sweep; with a next state (pipe->next) its level-0 reduce into the other level-1 region goes with it, in one of
+    // three forms:
+    //   side stream: the lean reduce (302 registers) runs there, next to the wavefronts of the bandwidth-bound forward sweep (193)
+    //   d <= 6:      forward sweep and reduce are the two wavefronts of one workgroup per tile (k_forward_reduce_cq): the records are
+    //                read from HBM once
+    //   d = 7, 8:    the two-wavefront kernel does not fit 256 registers; the lean reduce simply follows the forward sweep on this
+    //                stream (correct, nothing overlapped)
+    const CqArgs* next = pipe ? pipe->next : nullptr;
+    hipStream_t side = pipe ? pipe->side : nullptr;
+    SweepArgs an = a0;
+    if (next) {
         bind_up(with_l1_region(P0, 1 - region), 0, ws, an);
-        pipe->owner->ahead_region = 1 - region;
         an.part = nullptr;
-        if (a0.lv.nt >= 2) hipLaunchKernelGGL((k_forward_cq<D, 2>), grid, block, 0, st, a0, q);
-        else hipLaunchKernelGGL((k_forward_cq<D>), grid, block, 0, st, a0, q);
-        MFGM_CHECK_LAUNCH();
-        hipLaunchKernelGGL((k_reduce_cq_lean<D>), grid, block, 0, st, an, *pipe->next);
-        MFGM_CHECK_LAUNCH();
-        if (only_stage < 0 && (logdet || quad)) {
-            hipLaunchKernelGGL(k_sum_partials, dim3(P.B), dim3(256), 0, st, ws + P.off_part[0], P.lv[0].P, P.lv[0].Lpad, logdet, quad);
-            MFGM_CHECK_LAUNCH();
-        }
-        return 0;
-    }
-    if (pipe && pipe->next && !pipe->side) {
-        // forward sweep of this factorisation and level-0 reduce of the NEXT one as the two wavefronts of one workgroup per tile
-        // (k_forward_reduce_cq): the records are read from HBM once; the reduce's separator system goes to the other level-1 region
-        SweepArgs an = a0;
-        bind_up(with_l1_region(P0, 1 - region), 0, ws, an);
         pipe->owner->ahead_region = 1 - region;
-        CqArgs qf = q;
-        qf.site_lin2 = pipe->next->site_lin; qf.site_sym2 = pipe->next->site_sym;
-        qf.pre_Dhat = an.uDhat; qf.pre_Rsub = an.uRsub; qf.pre_S = an.uS; qf.pre_rhat = an.urhat; qf.pre_rho = an.urho;
-        if (a0.lv.nt >= 1) hipLaunchKernelGGL((k_forward_reduce_cq<D, 1>), grid, dim3(128), 0, st, a0, qf);
-        else hipLaunchKernelGGL((k_forward_reduce_cq<D>), grid, dim3(128), 0, st, a0, qf);
-        MFGM_CHECK_LAUNCH();
-        if (only_stage < 0 && (logdet || quad)) {
-            hipLaunchKernelGGL(k_sum_partials, dim3(P.B), dim3(256), 0, st, ws + P.off_part[0], P.lv[0].P, P.lv[0].Lpad, logdet, quad);
-            MFGM_CHECK_LAUNCH();
-        }
-        return 0;
     }
-    if (pipe && pipe->next) {
-        // the level-0 reduce of the NEXT factorisation's state, into the other level-1 region, on the side stream: from here on the main
-        // stream runs the bandwidth-bound level-0 forward sweep (193 registers), next to whose wavefronts the lean reduce (302) fits
+    if (next && side) {
         if (hipEventRecord(pipe->owner->ev[0], st) != hipSuccess) return 3;
-        if (hipStreamWaitEvent(pipe->side, pipe->owner->ev[0], 0) != hipSuccess) return 3;
-        SweepArgs an = a0;
-        bind_up(with_l1_region(P0, 1 - region), 0, ws, an);
-        pipe->owner->ahead_region = 1 - region;
-        an.part = nullptr;
-        hipLaunchKernelGGL((k_reduce_cq_lean<D>), grid, block, 0, pipe->side, an, *pipe->next);
+        if (hipStreamWaitEvent(side, pipe->owner->ev[0], 0) != hipSuccess) return 3;
+        hipLaunchKernelGGL((k_reduce_cq_lean<D>), grid, block, 0, side, an, *next);
         MFGM_CHECK_LAUNCH();
     }
     if (only_stage < 0 || only_stage == 1) {
-        if (a0.lv.nt >= 2) hipLaunchKernelGGL((k_forward_cq<D, 2>), grid, block, 0, st, a0, q);
-        else hipLaunchKernelGGL((k_forward_cq<D>), grid, block, 0, st, a0, q);
+        bool rides = false;                          // the next state's reduce rides in the forward kernel
+        if constexpr (D <= 6) {
+            if (next && !side) {
+                rides = true;
+                CqArgs qf = q;
+                qf.site_lin2 = next->site_lin; qf.site_sym2 = next->site_sym;
+                qf.pre_Dhat = an.uDhat; qf.pre_Rsub = an.uRsub; qf.pre_S = an.uS; qf.pre_rhat = an.urhat; qf.pre_rho = an.urho;
+                if (a0.lv.nt >= 1) hipLaunchKernelGGL((k_forward_reduce_cq<D, 1>), grid, dim3(128), 0, st, a0, qf);
+                else hipLaunchKernelGGL((k_forward_reduce_cq<D>), grid, dim3(128), 0, st, a0, qf);
+            }
+        }
+        if (!rides) {
+            if (a0.lv.nt >= 2) hipLaunchKernelGGL((k_forward_cq<D, 2>), grid, block, 0, st, a0, q);
+            else hipLaunchKernelGGL((k_forward_cq<D>), grid, block, 0, st, a0, q);
+        }
         MFGM_CHECK_LAUNCH();
+        if (next && !side && !rides) {
+            hipLaunchKernelGGL((k_reduce_cq_lean<D>), grid, block, 0, st, an, *next);
+            MFGM_CHECK_LAUNCH();
+        }
     }
-    if (only_stage < 0 && (logdet || quad)) {
-        hipLaunchKernelGGL(k_sum_partials, dim3(P.B), dim3(256), 0, st, ws + P.off_part[0], P.lv[0].P, P.lv[0].Lpad, logdet, quad);
-        MFGM_CHECK_LAUNCH();
-    }
+    if (logdet || quad) return sum_level0_partials(P, ws, P.lv[0].Lpad, logdet, quad, st);
     return 0;
 }
 
@@ -403,7 +406,6 @@ int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double
     // only_stage (profiling): 0 the two level-0 reduces, 1 the level-0 forward pair, 2 the joint up phase of the levels above, 3 their
     // joint backward pass
     const auto on = [&](int s) { return only_stage < 0 || only_stage == s; };
-    const int K = P.nlevels - 1;
     const size_t sh = P.off_pair - P.off_Dhat[1];
     double* ws2 = ws + sh;                            // (only the offsets of levels >= 1 are ever added to it)
     SweepArgs a0;
@@ -429,22 +431,8 @@ int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double
         hipLaunchKernelGGL((k_reduce_cq<D>), grid, block, 0, st, a1, q2);
         MFGM_CHECK_LAUNCH();
     }
-    const int lf = coarse_fuse_from(P);
-    for (int l = 1; l < K && l < lf && on(2); ++l) {
-        const SweepArgs a = coarse_level_args(P, l, ws, info), b = coarse_level_args(P, l, ws2, info);
-        hipLaunchKernelGGL((k_reduce_pair<D>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
-        MFGM_CHECK_LAUNCH();
-    }
-    if (lf <= K && on(2)) {
-        hipLaunchKernelGGL((k_coarse_factor_pair<D, true>), dim3(2 * P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p(), sh);
-        MFGM_CHECK_LAUNCH();
-    }
-    for (int l = std::min(K, lf - 1); l >= 1 && on(2); --l) {
-        const SweepArgs a = coarse_level_args(P, l, ws, info), b = coarse_level_args(P, l, ws2, info);
-        if (l < K) hipLaunchKernelGGL((k_forward_pair<D, true>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
-        else hipLaunchKernelGGL((k_forward_pair<D, false>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
-        MFGM_CHECK_LAUNCH();
-    }
+    if (on(2))
+        if (int rc = coarse_up_pair<D>(P, ws, sh, info, st)) return rc;
     if (!on(1)) {
         // (profiling call for another stage)
     } else if constexpr (D <= 6) {
@@ -462,36 +450,9 @@ int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double
         }
         MFGM_CHECK_LAUNCH();
     }
-    if (only_stage < 0 && (logdet || quad)) {
-        hipLaunchKernelGGL(k_sum_partials, dim3(P.B), dim3(256), 0, st, ws + P.off_part[0], P.lv[0].P, P.lv[0].Lpad, logdet, quad);
-        MFGM_CHECK_LAUNCH();
-    }
-    if (lf <= K && on(3)) {
-        hipLaunchKernelGGL((k_coarse_backward_pair<D, true>), dim3(2 * P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p(), sh);
-        MFGM_CHECK_LAUNCH();
-    }
-    for (int l = std::min(K, lf - 1); l >= 1 && on(3); --l) {
-        const SweepArgs a = coarse_level_args(P, l, ws, nullptr), b = coarse_level_args(P, l, ws2, nullptr);
-        if (l < K) hipLaunchKernelGGL((k_backward_pair<D, true>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
-        else hipLaunchKernelGGL((k_backward_pair<D, false>), dim3(2 * (a.lv.Lpad / 64)), block, 0, st, a, b);
-        MFGM_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-template <int D>
-int cq_coarse_backward(const Plan& P, double* ws, hipStream_t st) {
-    const int K = P.nlevels - 1;
-    const int lf = coarse_fuse_from(P);
-    if (lf <= K) {
-        int rc = launch_coarse_backward<D>(P, lf, true, ws, st);
-        if (rc) return rc;
-    }
-    for (int l = std::min(K, lf - 1); l >= 1; --l) {
-        SweepArgs a = coarse_level_args(P, l, ws, nullptr);
-        int rc = launch_backward<D>(a, true, l < K, false, st, true);
-        if (rc) return rc;
-    }
+    if (logdet || quad)
+        if (int rc = sum_level0_partials(P, ws, P.lv[0].Lpad, logdet, quad, st)) return rc;
+    if (on(3)) return coarse_down_pair<D>(P, ws, sh, st);
     return 0;
 }
 
@@ -500,10 +461,8 @@ int cq_selinv_girsanov_impl(const Plan& P, const CqArgs& q, const double* Lg, co
                             hipStream_t st, int only_level, bool alt = false) {
     // alt: the factorisation's levels >= 1 are the second copy (the second one of mfgm_cq_factor_pair)
     double* wsc = alt ? ws + (P.off_pair - P.off_Dhat[1]) : ws;
-    if (only_level != 0) {
-        int rc = cq_coarse_backward<D>(P, wsc, st);
-        if (rc) return rc;
-    }
+    if (only_level != 0)
+        if (int rc = coarse_down<D>(P, wsc, true, st)) return rc;
     SweepArgs a;
     memset(&a, 0, sizeof(a));
     a.lv = P.lv[0];
@@ -522,10 +481,8 @@ int cq_selinv_girsanov_impl(const Plan& P, const CqArgs& q, const double* Lg, co
 template <int D>
 int cq_selinv_kl_impl(const Plan& P, const CqArgs& q, const double* Lg, const double* yg, const SdeParams& pr, double* Sig, double* x,
                       double* kl, double* ws, hipStream_t st, int only_level) {
-    if (only_level != 0) {
-        int rc = cq_coarse_backward<D>(P, ws, st);
-        if (rc) return rc;
-    }
+    if (only_level != 0)
+        if (int rc = coarse_down<D>(P, ws, true, st)) return rc;
     if (only_level > 0) return 0;                    // profiling: the levels above the finest one alone
     SweepArgs a;
     memset(&a, 0, sizeof(a));
@@ -537,9 +494,7 @@ int cq_selinv_kl_impl(const Plan& P, const CqArgs& q, const double* Lg, const do
     if (a.lv.nt >= 2) hipLaunchKernelGGL((k_backward_kl_cq<D, 2>), dim3(a.lv.Lpad / 64), dim3(64), 0, st, a, pr, q);
     else hipLaunchKernelGGL((k_backward_kl_cq<D>), dim3(a.lv.Lpad / 64), dim3(64), 0, st, a, pr, q);
     MFGM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_sum_partials, dim3(P.B), dim3(256), 0, st, a.part, a.lv.P, 0, kl, (double*)nullptr);
-    MFGM_CHECK_LAUNCH();
-    return 0;
+    return sum_level0_partials(P, ws, 0, kl, nullptr, st);
 }
 
 template <int D>
@@ -693,6 +648,17 @@ bool cq_ok(const mfgm_plan* plan, const mfgm_cq_state* q) {
     if (q->slot && (!q->site_lin || !q->site_sym)) return false;
     return true;
 }
+// the pair calls: one dyn (same array, same layout) with two sets of observation sites, two distinct sets of outputs
+bool cq_pair_ok(const mfgm_plan* plan, const mfgm_cq_state* q, const mfgm_cq_state* q_next, const double* L, const double* y,
+                const double* L2, const double* y2, const void* ws, const int* info) {
+    if (!cq_ok(plan, q) || !cq_ok(plan, q_next) || !L || !y || !L2 || !y2 || L2 == L || y2 == y || !ws || !info) return false;
+    return plan->p.off_pair != 0 && q_next->dyn == q->dyn && q_next->slot == q->slot && q_next->p0_off == q->p0_off &&
+           q_next->d_off == q->d_off && q_next->s_off == q->s_off;
+}
+// the heads forms park the shared elimination in `scratch` (the parked stores must not leave the array)
+bool cq_heads_ok(const mfgm_plan* plan, int stride, const double* scratch, size_t scratch_doubles) {
+    return scratch && stride >= 2 && plan->p.lv[0].R % stride == 0 && scratch_doubles >= mfgm_cq_heads_scratch_doubles(plan, stride);
+}
 
 }  // namespace
 
@@ -770,8 +736,7 @@ int mfgm_cq_selinv_girsanov(const mfgm_plan* plan, int only_level, const mfgm_cq
                             const mfgm_sde_params* prm, double* dyn_out, void* ws, void* stream) {
     if (!cq_ok(plan, q) || !L || !y || !prm || !dyn_out || !ws || dyn_out == q->dyn || prm->kind != 0) return 1;
     const Plan& P = plan->p;
-    SdeParams pr;
-    memcpy(&pr, prm, sizeof(pr));
+    const SdeParams pr = sde_params(prm);
     CqArgs c = cq_args(q);
     c.dyn_out = dyn_out;
     MFGM_DISPATCH_D(P.d, (cq_selinv_girsanov_impl<DD>(P, c, L, y, pr, (double*)ws, (hipStream_t)stream, only_level)));
@@ -779,11 +744,7 @@ int mfgm_cq_selinv_girsanov(const mfgm_plan* plan, int only_level, const mfgm_cq
 
 int mfgm_cq_factor_pair(const mfgm_plan* plan, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y, double* logdet,
                         double* quad, double* L2, double* y2, void* ws, int* info, void* stream) {
-    if (!cq_ok(plan, q) || !cq_ok(plan, q_next) || !L || !y || !L2 || !y2 || L2 == L || y2 == y || !ws || !info) return 1;
-    // one dyn, two sets of observation sites
-    if (plan->p.off_pair == 0 || q_next->dyn != q->dyn || q_next->slot != q->slot || q_next->p0_off != q->p0_off ||
-        q_next->d_off != q->d_off || q_next->s_off != q->s_off)
-        return 1;
+    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info)) return 1;
     const Plan& P = plan->p;
     const CqArgs c = cq_args(q), c2 = cq_args(q_next);
     MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, logdet, quad, L2, y2, (double*)ws, info, (hipStream_t)stream)));
@@ -791,8 +752,7 @@ int mfgm_cq_factor_pair(const mfgm_plan* plan, const mfgm_cq_state* q, const mfg
 
 int mfgm_cq_factor_pair_stage(const mfgm_plan* plan, int stage, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y,
                               double* L2, double* y2, void* ws, int* info, void* stream) {
-    if (!cq_ok(plan, q) || !cq_ok(plan, q_next) || !L || !y || !L2 || !y2 || L2 == L || y2 == y || !ws || !info) return 1;
-    if (plan->p.off_pair == 0 || q_next->dyn != q->dyn || q_next->slot != q->slot || stage < 0 || stage > 3) return 1;
+    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info) || stage < 0 || stage > 3) return 1;
     const Plan& P = plan->p;
     const CqArgs c = cq_args(q), c2 = cq_args(q_next);
     MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, nullptr, nullptr, L2, y2, (double*)ws, info, (hipStream_t)stream, stage)));
@@ -805,20 +765,10 @@ size_t mfgm_cq_heads_scratch_doubles(const mfgm_plan* plan, int stride) {
     return (size_t)P.lv[0].Lpad * (P.lv[0].R / stride) * E;
 }
 
-static bool cq_pair_heads_ok(const mfgm_plan* plan, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next, const double* L,
-                             const double* y, const double* L2, const double* y2, const double* scratch, size_t scratch_doubles, const void* ws,
-                             const int* info) {
-    if (!cq_ok(plan, q) || !cq_ok(plan, q_next) || !L || !y || !L2 || !y2 || L2 == L || y2 == y || !scratch || !ws || !info) return false;
-    if (stride < 2 || plan->p.lv[0].R % stride != 0 || plan->p.off_pair == 0) return false;
-    if (scratch_doubles < mfgm_cq_heads_scratch_doubles(plan, stride)) return false;      // (the parked stores would leave the array)
-    return q_next->dyn == q->dyn && q_next->slot == q->slot && q_next->p0_off == q->p0_off && q_next->d_off == q->d_off &&
-           q_next->s_off == q->s_off;
-}
-
 int mfgm_cq_factor_pair_heads(const mfgm_plan* plan, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y,
                               double* logdet, double* quad, double* L2, double* y2, double* scratch, size_t scratch_doubles, void* ws, int* info,
                               void* stream) {
-    if (!cq_pair_heads_ok(plan, stride, q, q_next, L, y, L2, y2, scratch, scratch_doubles, ws, info)) return 1;
+    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info) || !cq_heads_ok(plan, stride, scratch, scratch_doubles)) return 1;
     const Plan& P = plan->p;
     const CqArgs c = cq_args(q), c2 = cq_args(q_next);
     MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, logdet, quad, L2, y2, (double*)ws, info, (hipStream_t)stream, -1, scratch,
@@ -828,7 +778,9 @@ int mfgm_cq_factor_pair_heads(const mfgm_plan* plan, int stride, const mfgm_cq_s
 int mfgm_cq_factor_pair_heads_stage(const mfgm_plan* plan, int stage, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next,
                                     double* L, double* y, double* L2, double* y2, double* scratch, size_t scratch_doubles, void* ws, int* info,
                                     void* stream) {
-    if (!cq_pair_heads_ok(plan, stride, q, q_next, L, y, L2, y2, scratch, scratch_doubles, ws, info) || stage < 0 || stage > 3) return 1;
+    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info) || !cq_heads_ok(plan, stride, scratch, scratch_doubles) || stage < 0 ||
+        stage > 3)
+        return 1;
     const Plan& P = plan->p;
     const CqArgs c = cq_args(q), c2 = cq_args(q_next);
     MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, nullptr, nullptr, L2, y2, (double*)ws, info, (hipStream_t)stream, stage,
@@ -839,8 +791,7 @@ int mfgm_cq_selinv_girsanov_alt(const mfgm_plan* plan, int only_level, const mfg
                                 const mfgm_sde_params* prm, double* dyn_out, void* ws, void* stream) {
     if (!cq_ok(plan, q) || !L2 || !y2 || !prm || !dyn_out || !ws || dyn_out == q->dyn || prm->kind != 0 || plan->p.off_pair == 0) return 1;
     const Plan& P = plan->p;
-    SdeParams pr;
-    memcpy(&pr, prm, sizeof(pr));
+    const SdeParams pr = sde_params(prm);
     CqArgs c = cq_args(q);
     c.dyn_out = dyn_out;
     MFGM_DISPATCH_D(P.d, (cq_selinv_girsanov_impl<DD>(P, c, L2, y2, pr, (double*)ws, (hipStream_t)stream, only_level, true)));
@@ -852,8 +803,7 @@ int mfgm_cq_selinv_kl(const mfgm_plan* plan, int only_level, const mfgm_cq_state
     if (!cq_ok(plan, q) || !L || !y || !prm || !kl_part || !ws || prm->kind != 0) return 1;
     if ((obs_mu != nullptr) != (obs_cov != nullptr) || (Sig != nullptr) != (x != nullptr)) return 1;
     const Plan& P = plan->p;
-    SdeParams pr;
-    memcpy(&pr, prm, sizeof(pr));
+    const SdeParams pr = sde_params(prm);
     CqArgs c = cq_args(q);
     c.obs_mu = obs_mu; c.obs_cov = obs_cov;
     MFGM_DISPATCH_D(P.d, (cq_selinv_kl_impl<DD>(P, c, L, y, pr, Sig, x, kl_part, (double*)ws, (hipStream_t)stream, only_level)));
@@ -1068,9 +1018,7 @@ int mfgm_packed_selinv_girsanov(const mfgm_plan* plan, int only_level, const dou
     if (n1 == q1 || nd == qd || ns == S) return 1;            // the update is out of place (see mfgm_girsanov.h)
     const Plan& P = plan->p;
     if (P.wide || P.nlevels < 2 || only_level >= P.nlevels || prm->kind != 0) return 1;
-    static_assert(sizeof(mfgm_sde_params) == sizeof(mfgm::SdeParams), "public and internal SDE parameter structs must match");
-    SdeParams pr;
-    memcpy(&pr, prm, sizeof(pr));
+    const SdeParams pr = sde_params(prm);
     GirsanovArgs g{q1, qd, n1, nd, ns, nullptr};
     hipStream_t st = (hipStream_t)stream;
     MFGM_DISPATCH_D(P.d, (selinv_girsanov_impl<DD>(P, L, S, aS, y, pr, g, (double*)ws, st, only_level)));
@@ -1081,8 +1029,7 @@ int mfgm_packed_selinv_kl(const mfgm_plan* plan, int only_level, const double* L
     if (!plan || !L || !S || !y || !prm || !Sig || !x || !kl_part || !ws) return 1;
     const Plan& P = plan->p;
     if (P.wide || P.nlevels < 2 || only_level >= P.nlevels || prm->kind != 0) return 1;
-    SdeParams pr;
-    memcpy(&pr, prm, sizeof(pr));
+    const SdeParams pr = sde_params(prm);
     hipStream_t st = (hipStream_t)stream;
     MFGM_DISPATCH_D(P.d, (selinv_kl_impl<DD>(P, L, S, aS, y, pr, Sig, x, kl_part, (double*)ws, st, only_level)));
 }
