@@ -1147,6 +1147,53 @@ int mfgm_panel_predict_lik(const mfgm_plan* plan, const mfgm_panel_data* data, i
 int mfgm_panel_site_update(const mfgm_panel_data* data, const double* g1, const double* g2, double lr, double* nat1, double* nat2,
                            void* stream);
 
+/* ---- factor-analysis sparse CVI (factor_analysis_variational.py; markovflow/kernels/sde_kernel.py:881; csrc/mfgm_fa.h) ------------------
+ * Sparse CVI on pairs of inducing states whose state stacks L independent latent processes g_l (the layout of mfgm_ml_data), observed
+ * through P outputs that mix them:  f_p(t_i) = sum_l W_ipl g_l(t_i).  The pair covariance enters through the L x L latent covariance
+ * of a point only, and the site update through an L x L matrix of mixed gradients.  Symmetric L x L matrices are given as their lower
+ * triangle, row-major, LT = L (L + 1) / 2 doubles: (l, l') with l' <= l at l (l + 1) / 2 + l'.  Device pointers. */
+typedef struct mfgm_fa_data {
+    int M, L, P, N;            /* inducing states; latents 1..8; outputs 1..64; time points */
+    int dl[8];                 /* D = sum dl, 2 <= D <= 32; latent l owns slots off_l .. off_l+dl[l] of both halves */
+    const int* seg;            /* [M + 2] CSR offsets per interval, as mfgm_sparse_data */
+    const double* h;           /* [N, 2D]  one row carries all L projections (as mfgm_ml_data) */
+    const double* c;           /* [N, L]   conditional variance of g_l(t_i) given the pair */
+    const double* w;           /* weights: [P, L] if w_stride == 0, [N, P, L] if w_stride == P*L */
+    long long w_stride;
+    const double* prior_mean;  /* [D] */
+    const double* prior_cov;   /* [D, D] */
+} mfgm_fa_data;
+typedef struct mfgm_fa_lik { int kind[64]; double param[64]; } mfgm_fa_lik;   /* per output: 0 everywhere = prediction only, else
+                                                                                MFGM_LIK_GAUSSIAN / BERNOULLI / POISSON */
+/* Contract (fp64).  pmu_m / PC_m: the mean / covariance of the pair of interval m assembled from mu [M, D], Sig, Sub [M, D, D] as
+ * mfgm_sparse_predict assembles them (the prior's initial state at both ends).  Per point i of interval m:
+ *     a_il       = sum_{r in slots(l)} h_ir pmu_m[r]
+ *     K_i[l, l'] = sum_{r in slots(l), s in slots(l')} h_ir PC_m[r][s] h_is + delta_ll' c_il
+ *     fmu_ip     = sum_l W_ipl a_il,     fvar_ip = sum_{l, l'} W_ipl W_ipl' K_i[l, l']          (not clamped)
+ *     (ve, dm, dv)_ip = (VE, dVE/dmu, dVE/dv) of mfgm_scalar_lik at (fmu_ip, fvar_ip, y_ip); the Gaussian formula is that of the readout
+ *         section above; a NaN y_ip gives ve = dm = dv = 0 exactly, fmu / fvar still written
+ *     gam1_il    = sum_p (dm_ip - 2 dv_ip fmu_ip) W_ipl,     gam2_i[l, l'] = sum_p dv_ip W_ipl W_ipl'.
+ * mfgm_fa_predict_lik: y, fmu, fvar, dm, dv [N, P]; lmu = a, gam1 [N, L]; lcov = K, gam2 [N, LT]; ve_part [M + 1] = the interval's sum
+ * of ve_ip in a fixed order (0 for an empty interval).  Any output may be NULL and is then not written.  With all kinds 0, y, ve_part,
+ * dm, dv, gam1 and gam2 must be NULL; kinds are 0 for every output or a likelihood for every output. */
+int mfgm_fa_predict_lik(const mfgm_fa_data* data, const mfgm_fa_lik* lik, const double* y, const double* mu, const double* Sig,
+                        const double* Sub, double* fmu, double* fvar, double* lmu, double* lcov, double* ve_part, double* dm, double* dv,
+                        double* gam1, double* gam2, void* stream);
+/* In place, for nat1 [M + 1, 2D] and nat2 [M + 1, 2D, 2D] (dense, both triangles written and symmetric to the bit) or the
+ * quadrant-packed nat2q [M + 1, D (D + 1) + D^2] of mfgm_sparse_factor_q, with l(r) the latent that owns slot r:
+ *     nat1[m][r]    <- (1 - lr) old + lr sum_{i in m} gam1[i, l(r)] h_ir
+ *     nat2[m][r][s] <- (1 - lr) old + lr sum_{i in m} gam2_i[l(r), l(s)] h_ir h_is.
+ * An empty interval decays only.  w is not read: the mixing was folded into gam by mfgm_fa_predict_lik.
+ * All three entry points: no allocation, no host synchronisation (graph-capturable), no atomics; one owner per output entry and a
+ * fixed order of summation, so two launches on the same inputs agree bit for bit.  They return 1 before any launch for L outside
+ * 1 .. 8, P outside 1 .. 64, a dl < 1, D outside 2 .. 32, w_stride other than 0 or P L, an unknown kind, a parameter outside the ranges of
+ * mfgm_scalar_lik / mfgm_pep_sites, lr outside [0, 1], or a missing pointer when N > 0.  N = 0 is valid: predict is a no-op (nothing
+ * is written, ve_part included) and the site update decays. */
+int mfgm_fa_site_update(const mfgm_fa_data* data, const double* gam1, const double* gam2, double lr, double* nat1, double* nat2,
+                        void* stream);
+int mfgm_fa_site_update_q(const mfgm_fa_data* data, const double* gam1, const double* gam2, double lr, double* nat1, double* nat2q,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

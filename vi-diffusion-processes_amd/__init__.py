@@ -20,4 +20,7 @@ def __getattr__(name):
     if name == "PanelSparseCVI":
         from .panel_variational_cvi import PanelSparseCVI
         return PanelSparseCVI
+    if name == "FactorAnalysisSparseCVI":
+        from .factor_analysis_variational import FactorAnalysisSparseCVI
+        return FactorAnalysisSparseCVI
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -176,6 +176,9 @@ EXPORTS = {
     "mfgm_panel_theta": (ctypes.c_int, [ctypes.c_void_p] * 10),
     "mfgm_panel_predict_lik": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 11),
     "mfgm_panel_site_update": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
+    "mfgm_fa_predict_lik": (ctypes.c_int, [ctypes.c_void_p] * 16),
+    "mfgm_fa_site_update": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
+    "mfgm_fa_site_update_q": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
 }
 
 
@@ -231,6 +234,18 @@ class MlLik(ctypes.Structure):
 
 
 ML_NONE, ML_MULTISTAGE, ML_HETGAUSS = 0, 1, 2
+
+
+class FaData(ctypes.Structure):
+    """mfgm_fa_data (include/mfgm.h)."""
+    _fields_ = [("M", ctypes.c_int), ("L", ctypes.c_int), ("P", ctypes.c_int), ("N", ctypes.c_int), ("dl", ctypes.c_int * 8),
+                ("seg", ctypes.c_void_p), ("h", ctypes.c_void_p), ("c", ctypes.c_void_p), ("w", ctypes.c_void_p),
+                ("w_stride", ctypes.c_longlong), ("prior_mean", ctypes.c_void_p), ("prior_cov", ctypes.c_void_p)]
+
+
+class FaLik(ctypes.Structure):
+    """mfgm_fa_lik (include/mfgm.h)."""
+    _fields_ = [("kind", ctypes.c_int * 64), ("param", ctypes.c_double * 64)]
 
 
 class PanelData(ctypes.Structure):

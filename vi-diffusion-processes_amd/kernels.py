@@ -809,6 +809,79 @@ class IndependentMultiOutput(Sum):
         return _emission_model(self._emission_matrix(), time_points)
 
 
+class FactorAnalysisKernel(IndependentMultiOutput):
+    """sde_kernel.py:881-941: output_dim observable processes that mix L = len(kernels) independent latent GPs linearly,
+        f_p(t) = sum_l W_pl(t) g_l(t),   W(t) = A(t) B,
+    with A a known, possibly time-dependent weight matrix and B [L, L] the loading matrix (identity at construction).  The state and
+    the prior state-space model are those of IndependentMultiOutput over the same children (`latent_components`); only the emission
+    differs: W(t) (H_1 (+) ... (+) H_L), materialised (the reference composes two emission models).
+
+    weight_function: a callable t [..., N] -> [..., N, output_dim, L], or a tensor A [output_dim, L] for time-invariant weights (the
+    emission model then carries `constant_matrix`).  `trainable` is kept for the reference's signature: B is assigned through
+    assign_loading_matrix by whatever optimiser the caller runs (FactorAnalysisSparseCVI.loading_grad gives its gradient)."""
+
+    def __init__(self, weight_function, kernels, output_dim, trainable=True, jitter=0.0):
+        kernels = list(kernels)
+        for k in kernels:
+            if isinstance(k, PiecewiseKernel):
+                raise NotImplementedError("FactorAnalysisKernel does not take PiecewiseKernel children: the stacked state is a Sum of "
+                                          "stationary kernels")
+            if isinstance(k, LatentExponentiallyGenerated):
+                raise NotImplementedError("FactorAnalysisKernel does not take LEG children: one scalar emission row per latent")
+        super().__init__(kernels, jitter)
+        self.latent_components = IndependentMultiOutput(kernels, jitter)
+        self.latent_dim = len(kernels)
+        self.output_dim = int(output_dim)
+        self.trainable = bool(trainable)
+        if callable(weight_function):
+            self._A, self._Afn = None, weight_function
+        else:
+            A = torch.as_tensor(weight_function, dtype=torch.float64)
+            if tuple(A.shape) != (self.output_dim, self.latent_dim):
+                raise ValueError(f"constant weights must be [output_dim, n_latents] = [{self.output_dim}, {self.latent_dim}], got "
+                                 f"{tuple(A.shape)}")
+            self._A, self._Afn = A, None
+        self._B = torch.eye(self.latent_dim, dtype=torch.float64)
+        self.loading_version = 0          # moves with every assign_loading_matrix: what caches of W are kept for
+
+    @property
+    def loading_matrix(self):
+        return self._B
+
+    def assign_loading_matrix(self, B):
+        B = torch.as_tensor(B, dtype=torch.float64).detach().to("cpu")
+        if tuple(B.shape) != (self.latent_dim, self.latent_dim):
+            raise ValueError(f"the loading matrix is [{self.latent_dim}, {self.latent_dim}], got {tuple(B.shape)}")
+        self._B = B.clone()
+        self.loading_version += 1
+
+    @property
+    def constant_weights(self):
+        """True when A does not depend on time."""
+        return self._A is not None
+
+    def base_weights(self, time_points):
+        """A(t): [P, L] for time-invariant weights, else [..., N, P, L], on the device of time_points."""
+        if self._A is not None:
+            return self._A.to(time_points.device)
+        A = torch.as_tensor(self._Afn(time_points), dtype=torch.float64).to(time_points.device)
+        if tuple(A.shape) != tuple(time_points.shape) + (self.output_dim, self.latent_dim):
+            raise ValueError(f"weight_function must return {tuple(time_points.shape) + (self.output_dim, self.latent_dim)}, got "
+                             f"{tuple(A.shape)}")
+        return A
+
+    def weights(self, time_points):
+        """W(t) = A(t) B: [P, L] for time-invariant weights, else [..., N, P, L]."""
+        return self.base_weights(time_points) @ self._B.to(time_points.device)
+
+    def generate_emission_model(self, time_points):
+        H = self._emission_matrix().to(time_points.device)          # H_1 (+) ... (+) H_L  [L, D]
+        W = self.weights(time_points)
+        if self._A is not None:
+            return _emission_model(W @ H, time_points)
+        return EmissionModel((W @ H).contiguous())
+
+
 class SparseSpatioTemporalKernel(IndependentMultiOutput):
     """spatio_temporal_variational.py:45-106: k((x, t), (x', t')) = k_s(x, x') k_t(t, t') with space marginalised to the Ms inducing
     locations Z_s -- f(Z_s, .) = chol(K_s(Z_s, Z_s)) [H_t s_1(.), ..., H_t s_Ms(.)] with s_j independent copies of the time kernel's
