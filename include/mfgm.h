@@ -671,6 +671,38 @@ int mfgm_packed_leg_ssm(const mfgm_plan* plan, const mfgm_leg_spec* spec, const 
  * any HIP call, for a null spec or pointer, d < 1, d > 8 or n < 0; n == 0 returns 0 without a launch. */
 int mfgm_leg_transitions(const mfgm_leg_spec* spec, long n, const double* time_deltas, double* A, double* Q, void* stream);
 
+/* Mean functions of a driven kernel SDE  dx = F x dt + u(t) dt + L dw  (markovflow/mean_function.py `ImpulseMeanFunction`,
+ * `StepMeanFunction`; csrc/mfgm_mean.h): the deterministic response to K actions at the times t_0 <= ... <= t_K-1 of each of B chains
+ * (ties allowed; the caller checks the order).  With A(dt) the transition of mfgm_packed_kernel_ssm on the same terms (the same
+ * closed forms, in registers; terms.mean and terms.jitter are ignored), d the terms' own state dimension:
+ *   coefficients   c_k = A(t_k - t_k-1) c_k-1 + rhs_k,   c_-1 = 0                        (impulses: rhs = u; steps: rhs = a_k-1 - a_k
+ *                                                                                          with a_k = -F^-1 u_k, a_-1 = 0)
+ *   mean           mu(t) = shift_k + A(t - t_k) c_k  with  k = #{i : t_i < t} - 1,  mu(t) = 0 when no t_i < t:  an action is not seen
+ *                  at its own time, only after it  (shift: NULL = 0 for impulses, a for steps).
+ * action_times [B, K], rhs / coef / shift [B, K, d], time_points [B, N] (unordered), state_mean [B, N, d], f_mean [B, N]: natural
+ * device arrays; emission: a HOST array of d doubles (the kernel's emission row), f_mean = emission . mu.
+ *
+ * mfgm_action_coefficients: the recurrence is serial in K; stationary transitions form a semigroup, A(a) A(b) = A(a + b), so it is
+ * scanned over segments of seg_len actions without a matrix product: one lane per (chain, segment) runs it from zero (local prefixes
+ * into coef, the segment's last value into ws), one lane per chain walks the S = ceil(K / seg_len) segment ends T_s,
+ * C_s = A(T_s - T_s-1) C_s-1 + p_s, and one lane per action of the segments s >= 1 adds A(t_k - T_s-1) C_s-1 -- the gap taken as a
+ * difference of two times.  At most three launches, no host synchronisation (graph-capturable), no atomics; every entry has one owner
+ * and a fixed order of operations, so two calls give identical bits; the result depends on seg_len (the grouping of the sums), not on
+ * the device.  seg_len = 0: the smallest s with s s >= K, a rule in K alone.  coef may alias rhs.
+ * ws: mfgm_action_workspace_doubles(B, K, d, seg_len) doubles (B S d; 0 for arguments the entry points reject).
+ *
+ * mfgm_action_mean: one lane per query point: binary search in the chain's action times, A(t - t_k), the mat-vec, the shift and the
+ * emission in registers; one launch.  state_mean and f_mean may each be NULL (both: nothing is launched); a NaN query point gives 0.
+ *
+ * Both return 1, before any HIP call, for a null required argument (emission when f_mean is given), B < 1, K < 1, seg_len < 0,
+ * N < 0, d > 8 and whatever terms mfgm_packed_kernel_ssm rejects.  N = 0 returns 0 and launches nothing. */
+size_t mfgm_action_workspace_doubles(int B, int K, int d, int seg_len);
+int mfgm_action_coefficients(const mfgm_kernel_terms* terms, int B, int K, int seg_len, const double* action_times, const double* rhs,
+                             double* coef, void* ws, void* stream);
+int mfgm_action_mean(const mfgm_kernel_terms* terms, int B, int K, long N, const double* action_times, const double* coef,
+                     const double* shift, const double* time_points, const double* emission, double* state_mean, double* f_mean,
+                     void* stream);
+
 /* VDP (markovflow/models/vi_sde.py `VariationalMarkovGP`): drift f_i(x) = af_i x - bf_i x^3, diagonal diffusion q,
  * q(x0) = N(mu0, chol0 chol0^T) (packed lower triangle), grid step dt, learning rate lr. */
 typedef struct mfgm_vdp_params {

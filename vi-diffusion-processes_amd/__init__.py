@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "PanelSparseCVI":
         from .panel_variational_cvi import PanelSparseCVI
         return PanelSparseCVI
+    if name in ("MeanFunction", "ZeroMeanFunction", "LinearMeanFunction", "ImpulseMeanFunction", "StepMeanFunction"):
+        from . import mean_function
+        return getattr(mean_function, name)
     if name == "FactorAnalysisSparseCVI":
         from .factor_analysis_variational import FactorAnalysisSparseCVI
         return FactorAnalysisSparseCVI

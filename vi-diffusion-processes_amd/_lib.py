@@ -69,6 +69,9 @@ EXPORTS = {
     "mfgm_packed_piecewise_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_leg_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_leg_transitions": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long] + [ctypes.c_void_p] * 4),
+    "mfgm_action_workspace_doubles": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "mfgm_action_coefficients": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 5),
+    "mfgm_action_mean": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_long] + [ctypes.c_void_p] * 8),
     "mfgm_vdp_workspace_doubles": (ctypes.c_size_t, [ctypes.c_void_p]),
     "mfgm_packed_vdp_to_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_vdp_to_naturals": (ctypes.c_int, [ctypes.c_void_p] * 10),

@@ -41,6 +41,13 @@ int piecewise_ssm_impl(const Plan& P, const KernelTermsDev& kt, const PiecewiseD
 // kernels do not take.
 int mfgm::device_terms(const Plan& P, const mfgm_kernel_terms& in, KernelTermsDev& kt, int (*src)[3]) {
     if (P.wide || P.d > 8) return 1;
+    int dim = 0;
+    if (device_terms(in, kt, src, dim)) return 1;
+    return dim != P.d;
+}
+
+// The same without a plan: the state dimension is the terms' own (d: out).
+int mfgm::device_terms(const mfgm_kernel_terms& in, KernelTermsDev& kt, int (*src)[3], int& d) {
     if (in.nterm < 1 || in.nterm > 8) return 1;
     memset(&kt, 0, sizeof(kt));
     kt.nterm = in.nterm;
@@ -81,9 +88,9 @@ int mfgm::device_terms(const Plan& P, const mfgm_kernel_terms& in, KernelTermsDe
         kt.offset[c] = dim;
         dim += n;
     }
-    if (dim != P.d) return 1;
     for (int i = 0; i < dim; ++i) kt.mean[i] = in.mean[i];
     kt.jitter = in.jitter;
+    d = dim;
     return 0;
 }
 

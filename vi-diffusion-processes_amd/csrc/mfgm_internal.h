@@ -73,6 +73,7 @@ int wide_kl_terms(const Plan& P, const double* Sig, const double* Sub, const dou
 // mfgm_api_kernel.hip: mfgm_kernel_terms -> the term kernels' form (mfgm_kernel_ssm.h)
 struct KernelTermsDev;
 int device_terms(const Plan& P, const mfgm_kernel_terms& in, KernelTermsDev& kt, int (*src)[3]);
+int device_terms(const mfgm_kernel_terms& in, KernelTermsDev& kt, int (*src)[3], int& d);      // no plan: d is the terms' own
 
 // mfgm_api_mfma.hip: which = 0 reduce, 1 forward, 2 backward
 struct WideArgs;

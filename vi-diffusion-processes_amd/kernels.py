@@ -187,6 +187,12 @@ class StationaryKernel:
             return torch.tensor([[0.0, 1.0], [-lam ** 2, -2.0 * lam]], dtype=torch.float64)
         return torch.tensor([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [-lam ** 3, -3.0 * lam ** 2, -3.0 * lam]], dtype=torch.float64)
 
+    @property
+    def generator_matrix(self):
+        """G with A(dt) = expm(G dt): feedback_matrix, except under a Product, whose feedback_matrix is the reference's (x) F_i while
+        its transitions are generated by the Kronecker sum.  What the step mean function solves against (mean_function.py)."""
+        return self.feedback_matrix
+
     # -- the device structs ---------------------------------------------------------------------------------------------------------------
     def _spec(self):
         comps = self._components()
@@ -481,6 +487,10 @@ class Sum(StationaryKernel):
     def feedback_matrix(self):
         return torch.block_diag(*[k.feedback_matrix for k in self.kernels])
 
+    @property
+    def generator_matrix(self):
+        return torch.block_diag(*[k.generator_matrix for k in self.kernels])
+
     def state_space_model(self, time_points, plan=None):
         # each component kernel adds its own jitter to its Q block; Sum adds its own on top (sde_kernel.py:640-656).  (The torch build
         # of a Matern tree beyond state_dim 8 has always used the Sum's jitter alone.)
@@ -730,6 +740,15 @@ class Product(StationaryKernel):
         for k in self.kernels[1:]:
             F = _kron(F, k.feedback_matrix)
         return F
+
+    @property
+    def generator_matrix(self):
+        """The Kronecker sum G_1 (+) G_2 (+) ...: A = (x) expm(G_i dt) = expm(((+) G_i) dt)."""
+        G = self.kernels[0].generator_matrix
+        for k in self.kernels[1:]:
+            g = k.generator_matrix
+            G = _kron(G, torch.eye(g.shape[-1], dtype=torch.float64)) + _kron(torch.eye(G.shape[-1], dtype=torch.float64), g)
+        return G
 
     def hyperparameter_leaves(self, device="cpu"):
         return [k.hyperparameter_leaves(device) for k in self.kernels]

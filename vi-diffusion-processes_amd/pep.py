@@ -37,7 +37,8 @@ class PowerExpectationPropagation(GaussianProcessWithSitesBase):
     """pep.py:28-247.  One chain: time points [N], observations [N, 1]."""
 
     def __init__(self, input_data, kernel, likelihood, mean_function=None, learning_rate=1.0, alpha=1.0):
-        super().__init__(input_data, kernel, likelihood, mean_function)
+        # mean_function is the reference's signature only here: PEP's sites are on f itself and the model has never used it
+        super().__init__(input_data, kernel, likelihood, None)
         if not 0.0 < float(alpha) <= 1.0:
             raise ValueError("alpha must lie in (0, 1]")
         if not 0.0 <= float(learning_rate) <= 1.0:

@@ -111,7 +111,7 @@ def interval_update(likelihood, alpha, lr, idx, w, c, y, mu, S, nat1, nat2, lnor
 class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
     """sparse_pep.py:41-559.  One chain: inducing points [M]; sites nat1 [M+1, 2d], nat2 [M+1, 2d, 2d], log_norm [M+1, 1].
     The sites are public and assignable; every nat2_m must be symmetric (the kernel reads its lower triangle, the torch route the whole
-    matrix).  `mean_function` is accepted for the reference's signature and ignored, as SparseCVIGaussianProcess ignores it.
+    matrix).  `mean_function` is accepted for the reference's signature and ignored here (SparseCVIGaussianProcess itself applies it).
     `likelihood` is a PEP wrapper (PEPScalarLikelihood / PEPGaussian); classic_elbo and predict_log_density use the likelihood it wraps.
     On CPU tensors the posterior comes from a dense (M d) x (M d) inverse: that route exists for small models and the host tests only."""
 
@@ -130,7 +130,7 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
                                       "stationary kernel on the whole axis")
         # the parent's objectives (classic_elbo, predict_log_density) take variational expectations: they get the wrapped likelihood
         base = likelihood if hasattr(likelihood, "variational_expectations") else likelihood.base
-        super().__init__(kernel, inducing_points, base, mean_function, float(learning_rate))
+        super().__init__(kernel, inducing_points, base, None, float(learning_rate))
         self._pep = likelihood
         self.alpha = float(alpha)
         M, n = inducing_points.shape[0], 2 * kernel.state_dim

@@ -49,6 +49,10 @@ class SparseCVIGaussianProcess:
             self.nat2 = torch.zeros((M + 1, 2 * sd, 2 * sd), dtype=dt, device=dev)
         self._dist_p = None
         self._shard = None
+        # a mean function of time (mean_function.py): the sites live on the zero-mean part g, the likelihood sees f = g + m
+        self._time_mean = mean_function
+        if shard is not None and mean_function is not None:
+            raise NotImplementedError("a chain shared between processes (shard=) does not take a mean function")
         if shard is not None:
             from .distributed import ChainShard
             if sd <= 8 or inducing_points.dim() != 1:
@@ -156,7 +160,7 @@ class SparseCVIGaussianProcess:
 
     @property
     def posterior(self):
-        return ConditionalProcess(self.dist_q, self._kernel, self.inducing_inputs)
+        return ConditionalProcess(self.dist_q, self._kernel, self.inducing_inputs, self._time_mean)
 
     def local_objective_and_gradients(self, Fmu, Fvar, Y):
         obj = self._likelihood.variational_expectations(Fmu, Fvar, Y).sum()
@@ -200,7 +204,7 @@ class SparseCVIGaussianProcess:
             sd = _lib.SparseData()
             sd.M, sd.d, sd.N, sd.m_lo, sd.m_hi = M, d, N, m_lo, m_hi
             sd.seg, sd.w, sd.c, sd.prior_mean, sd.prior_cov = seg.data_ptr(), w.data_ptr(), cc.data_ptr(), pm.data_ptr(), pc.data_ptr()
-            val = dict(struct=sd, keep=(seg, w, cc, pm, pc), N=N, own=own)
+            val = dict(struct=sd, keep=(seg, w, cc, pm, pc), N=N, own=own, t=time_points)
         if val is None and self._shard is not None:
             raise ValueError("a shared chain needs sorted, un-batched time points on the device")
         self._data_cache = (Stamp(input_data[0]), val)
@@ -327,8 +331,22 @@ class SparseCVIGaussianProcess:
             c = data["y_own"] = (Stamp(observations), observations[data["own"]])
         return c[1]
 
+    def _mean_at(self, data):
+        """m(t) [N, 1] at the owned data points of a fused data set, kept with it (the data cache goes with the kernel)."""
+        m = data.get("mean")
+        if m is None:
+            m = data["mean"] = self._time_mean(data["t"]).reshape(-1, 1).contiguous()
+        return m
+
     def _predict_f_data(self, data):
-        """(fmu, fvar) [N, 1] at the data points from the cached marginals (mfgm_sparse_predict)."""
+        """(fmu, fvar) [N, 1] at the data points: those of the zero-mean part, the mean shifted by the mean function."""
+        res = self._predict_g_data(data)
+        if self._time_mean is None:
+            return res
+        return res[0] + self._mean_at(data), res[1]
+
+    def _predict_g_data(self, data):
+        """(fmu, fvar) [N, 1] of the zero-mean part at the data points from the cached marginals (mfgm_sparse_predict)."""
         c = getattr(self, "_pred_cache", None)
         if c is not None and self._current(c[0]) and c[1] is data:
             return c[2]          # the sites have not moved since these were computed (the ELBO of the previous iteration)
@@ -364,6 +382,9 @@ class SparseCVIGaussianProcess:
         # observations every step, so that a likelihood's per-observation-tensor caches hit (a fresh slice object never would)
         grads = self._likelihood.ve_gradients_expectation(fx_mus, fx_covs, self._own_observations(data, observations))
         g1, g2 = grads[0].reshape(-1).contiguous(), grads[1].reshape(-1).contiguous()
+        if self._time_mean is not None:
+            # from the expectation parameters of f to those of g = f - m, which the sites are on: d/dmu - 2 d/dvar mu_g
+            g1 = g1 + 2.0 * g2 * self._mean_at(data).reshape(-1)
         pl = self.dist_p.plan
         self._sync_sites()
         if self._packed:
@@ -404,6 +425,8 @@ class SparseCVIGaussianProcess:
         time_points, observations = input_data
         fx_mus, fx_covs = self.posterior.predict_f(time_points)
         _, grads = self.local_objective_and_gradients(fx_mus, fx_covs, observations)
+        if self._time_mean is not None:
+            grads = (grads[0] + 2.0 * grads[1] * self._time_mean(time_points), grads[1])      # (as in update_sites)
         H = self._kernel.generate_emission_model(time_points).emission_matrix
         P, _ = conditional_statistics(time_points, self.inducing_inputs, self._kernel)
         theta_linear, lik_nat2 = back_project_nats(grads[0], grads[1], H @ P)
@@ -420,7 +443,7 @@ class SparseCVIGaussianProcess:
         data = self._data(input_data)
         if data is None:
             q = self.dist_q
-            fx_mus, fx_covs = ConditionalProcess(q, self._kernel, self.inducing_inputs).predict_f(time_points)
+            fx_mus, fx_covs = ConditionalProcess(q, self._kernel, self.inducing_inputs, self._time_mean).predict_f(time_points)
             ve = self._likelihood.variational_expectations(fx_mus, fx_covs, observations).sum()
             return ve - q.kl_divergence(self.dist_p).sum()
         fx_mus, fx_covs = self._predict_f_data(data)
@@ -477,6 +500,8 @@ class SparseCVIGaussianProcess:
         models.  What the reference's sparse notebooks get from a GradientTape over `model.loss` between two site steps.  One chain,
         every process its own: `shard=` is not covered."""
         from . import hyper
+        if self._time_mean is not None:
+            raise NotImplementedError("elbo_and_grad with a mean function is not implemented")
         hyper.precheck(self._kernel)
         if self._shard is not None:
             raise NotImplementedError("elbo_and_grad is not implemented for a chain shared between processes (shard=)")
@@ -494,6 +519,8 @@ class SparseCVIGaussianProcess:
         self._marg, self._pred_cache, self._kl_cache = None, None, None
         self.__dict__.pop("_theta_bufs", None)
         self.__dict__.pop("_sweep_bufs", None)
+        if hasattr(self._time_mean, "kernel_changed"):
+            self._time_mean.kernel_changed()
 
     def predict_log_density(self, input_data, full_output_cov=False):
         """log p(y* | data) per point (markovflow/models/models.py:206-227): the likelihood's predict_log_density of posterior.predict_f."""

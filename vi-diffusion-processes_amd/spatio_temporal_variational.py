@@ -56,7 +56,7 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
             raise ValueError(f"state dimension Ms * d_t = {Ms} * {d_t} = {Ms * d_t} exceeds the limit of {MAX_STATE_DIM}")
         kernel = SparseSpatioTemporalKernel(kernel_space, kernel_time, inducing_space)
         kernel._time_emission_row(inducing_time.device)          # raises for an emission that depends on time
-        super().__init__(kernel, inducing_time, likelihood, mean_function, learning_rate)
+        super().__init__(kernel, inducing_time, likelihood, None, learning_rate)       # (the mean here is a function of X, applied below)
         self._kernel_space, self._kernel_time = kernel_space, kernel_time
         self._inducing_space, self._mean_function = inducing_space, mean_function
         self.num_inducing_space, self.num_inducing_time = Ms, int(inducing_time.shape[0])

@@ -56,8 +56,11 @@ class GaussianProcessRegression:
     @property
     def _kalman(self):
         ssm = self._kernel.state_space_model(self._time_points)
-        return KalmanFilter(ssm, self._kernel.generate_emission_model(self._time_points), self._observations,
-                            self._chol_obs_covariance)
+        # the filter runs on the residuals y - m(t) (gaussian_process_regression.py:118-128)
+        y = self._observations
+        if self._mean_function is not None:
+            y = y - self._mean_function(self._time_points)
+        return KalmanFilter(ssm, self._kernel.generate_emission_model(self._time_points), y, self._chol_obs_covariance)
 
     def log_likelihood(self):
         return self._kalman.log_likelihood()
@@ -67,7 +70,11 @@ class GaussianProcessRegression:
         with respect to the kernel's hyper-parameters (the structure of kernel.hyperparameter_leaves(), 0-dim CPU fp64 tensors; N and
         R matrices for the LEG kernel) and to the scalar observation noise sigma^2 = chol_obs_covariance^2 (None when that is zero).
         One factorisation, one selected inverse and one score pass (hyper.py); the chains of a batch share the
-        hyper-parameters, so their scores are summed."""
+        hyper-parameters, so their scores are summed.  With a mean function the score is that of the residuals y - m(t); a mean that
+        depends on the kernel (impulse / step responses) has a hyper-parameter gradient of its own, which is not built."""
+        if getattr(self._mean_function, "depends_on_kernel", False):
+            raise NotImplementedError("log_likelihood_and_grad with a mean function that depends on the kernel: the mean's own "
+                                      "hyper-parameter gradient is not implemented")
         hyper.precheck(self._kernel)        # before the prior is built: a refused kernel launches nothing
         kf = self._kalman
         ll, grads, moments, disp = hyper.kernel_score(self._kernel, kf, self._time_points)
@@ -105,6 +112,17 @@ class GaussianProcessWithSitesBase:
         self._dist_p = None
         self._em = None
         self._cache = None
+        # the sites live on the zero-mean part g; the likelihood sees f = g + m
+        self._mean_function = mean_function
+        self._mean_data = None
+
+    def _mean_at_data(self):
+        """m(time_points) [..., T, 1], resident until kernel_changed(); None without a mean function."""
+        if self._mean_function is None:
+            return None
+        if self._mean_data is None:
+            self._mean_data = self._mean_function(self._time_points).contiguous()
+        return self._mean_data
 
     @property
     def time_points(self):
@@ -158,9 +176,8 @@ class GaussianProcessWithSitesBase:
 
     @property
     def posterior(self):
-        """variational_cvi.py:146-153: the posterior process on dist_q."""
-        # (no mean function: the constructor's `mean_function` is the reference's signature only, the sites models have never used it)
-        return ConditionalProcess(self.dist_q, self._kernel, self._time_points)
+        """variational_cvi.py:146-153: the posterior process on dist_q (of g), with the mean function added to f."""
+        return ConditionalProcess(self.dist_q, self._kernel, self._time_points, self._mean_function)
 
     @property
     def posterior_kalman(self):
@@ -194,13 +211,24 @@ class GaussianProcessWithSitesBase:
 
     def kernel_changed(self):
         """Drop everything derived from the kernel's hyper-parameters -- the prior state-space model (with the fused calls' caches and
-        scratch, which hang on it) and the emission model -- after kernel.assign_hyperparameters(); the sites stay."""
+        scratch, which hang on it), the emission model and the mean at the data (the mean function is told too) -- after
+        kernel.assign_hyperparameters(); the sites stay."""
         self._dist_p = None
         self._em = None
         self._cache = None
+        self._mean_data = None
+        if hasattr(self._mean_function, "kernel_changed"):
+            self._mean_function.kernel_changed()
 
     def predict_f_at_data(self):
-        """posterior.predict_f(self.time_points): at the conditioning points this is (H mu, H Sigma H^T) of dist_q."""
+        """posterior.predict_f(self.time_points): at the conditioning points this is (H mu, H Sigma H^T) of dist_q, the mean shifted by
+        the mean function (one add of a resident tensor)."""
+        fmu, fvar = self._predict_g_at_data()
+        m = self._mean_at_data()
+        return (fmu, fvar) if m is None else (fmu + m, fvar)
+
+    def _predict_g_at_data(self):
+        """predict_f_at_data of the zero-mean part g, which the sites are on."""
         fused = self._predict_f_fused()
         if fused is not None:
             return fused
@@ -315,6 +343,11 @@ class CVIGaussianProcess(GaussianProcessWithSitesBase):
         # (1 - lr) theta + lr g assigned to the site variables in place (tf.Variable.assign in the reference, :366-368), one launch
         # (torch._foreach_lerp_ on these two small tensors runs a 25 us multi-tensor kernel: 15 % of the config-2 step)
         n1, n2, g1, g2 = self.sites.nat1, self.sites.nat2, grads[0], grads[1]
+        m = self._mean_at_data()
+        if m is not None:
+            # the gradients came out with respect to [mu_f, var + mu_f^2]; the sites are on g = f - m, whose expectation parameters are
+            # [mu_g, var + mu_g^2]: d/dmu - 2 d/dvar mu_g = (d/dmu - 2 d/dvar mu_f) + 2 d/dvar m
+            g1 = g1 + 2.0 * g2.reshape(g1.shape) * m
         if n1.is_cuda and n1.is_contiguous() and n2.is_contiguous() and g1.shape == n1.shape and g2.numel() == n2.numel():
             g1, g2 = g1.contiguous(), g2.contiguous()
             _lib.check(_lib.load().mfgm_site_lerp(_ptr(n1), _ptr(g1), n1.numel(), _ptr(n2), _ptr(g2), n2.numel(), float(lr), _stream()),
@@ -345,6 +378,8 @@ class CVIGaussianProcess(GaussianProcessWithSitesBase):
         mu, cov = q.marginals
         Hb = H.expand(ssm.batch_shape + tuple(H.shape[-3:])).reshape(B, T, H.shape[-2], d)
         fmu = (Hb @ mu[..., None])[..., 0]
+        if self._mean_function is not None:
+            fmu = fmu + self._mean_at_data().expand(ssm.batch_shape + tuple(fmu.shape[-2:])).reshape(fmu.shape)
         fvar = torch.diagonal(Hb @ cov @ Hb.transpose(-1, -2), dim1=-2, dim2=-1)
         obs = self._observations.expand(ssm.batch_shape + tuple(self._observations.shape[-2:])).reshape(B, T, -1)
         ve = self._likelihood.variational_expectations(fmu, fvar, obs).sum()
@@ -354,6 +389,9 @@ class CVIGaussianProcess(GaussianProcessWithSitesBase):
         """classic_elbo as a differentiable function of the KERNEL's hyper-parameters (the sites held fixed): (elbo, leaves) with leaves
         the kernel's hyperparameter_leaves -- what the reference gets from a GradientTape over the kernel's tf.Variables
         (tests/integration/models/test_variational_cvi.py:93-110 with the kernel not frozen).  One chain; d <= 8."""
+        if getattr(self._mean_function, "depends_on_kernel", False):
+            raise NotImplementedError("classic_elbo_tape_hyper with a mean function that depends on the kernel: the mean's own "
+                                      "hyper-parameter gradient is not implemented")
         ssm = self.dist_p
         pl, T, d = ssm.plan, ssm.T, ssm.d
         if ssm.B != 1 or d > 8:
@@ -366,6 +404,8 @@ class CVIGaussianProcess(GaussianProcessWithSitesBase):
         mu, cov = q.marginals
         Hb = H.reshape(1, T, H.shape[-2], d)
         fmu = (Hb @ mu[..., None])[..., 0]
+        if self._mean_function is not None:
+            fmu = fmu + self._mean_at_data().reshape(fmu.shape)
         fvar = torch.diagonal(Hb @ cov @ Hb.transpose(-1, -2), dim1=-2, dim2=-1)
         ve = self._likelihood.variational_expectations(fmu, fvar, self._observations.reshape(1, T, -1)).sum()
         return ve - tape.kl_divergence_tape(q, p).sum(), leaves
