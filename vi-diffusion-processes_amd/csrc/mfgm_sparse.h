@@ -315,12 +315,16 @@ static __global__ __launch_bounds__(256) void k_sparse_sites(SparseArgs a, const
     const int d2 = 2 * a.d, tid = threadIdx.x, m0 = a.m_lo + blockIdx.x * G;
     const int ne = d2 * d2;            // even, and a row never splits a pair
     double2 old[8], acc[8];
-    int rr[SPI], cc[SPI];
+    // entry (r, c) is summed as (g w_max(r,c)) w_min(r,c): the same roundings at (r, c) and (c, r), so a symmetric site stays symmetric
+    // to the bit, and the same roundings as k_sparse_sites_q takes on the lower triangle it stores ((g w_r) w_c there is rounded
+    // otherwise than (g w_c) w_r: the two triangles used to differ in the last bit)
+    int hx[SPI], lx[SPI], hy[SPI], ly[SPI];
 #pragma unroll
     for (int kk = 0; kk < SPI; ++kk) {
         const int e = 2 * (tid + kk * 256);
-        rr[kk] = (e < ne) ? e / d2 : 0;
-        cc[kk] = (e < ne) ? e - rr[kk] * d2 : 0;
+        const int r = (e < ne) ? e / d2 : 0, c = (e < ne) ? e - r * d2 : 0;
+        hx[kk] = max(r, c); lx[kk] = min(r, c);
+        hy[kk] = max(r, c + 1); ly[kk] = min(r, c + 1);
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -354,9 +358,8 @@ static __global__ __launch_bounds__(256) void k_sparse_sites(SparseArgs a, const
                 const double gg = w[d2 + 1];
 #pragma unroll
                 for (int kk = 0; kk < SPI; ++kk) {
-                    const double gr = gg * w[rr[kk]];
-                    acc[gi * SPI + kk].x = __builtin_fma(gr, w[cc[kk]], acc[gi * SPI + kk].x);
-                    acc[gi * SPI + kk].y = __builtin_fma(gr, w[cc[kk] + 1], acc[gi * SPI + kk].y);
+                    acc[gi * SPI + kk].x = __builtin_fma(gg * w[hx[kk]], w[lx[kk]], acc[gi * SPI + kk].x);
+                    acc[gi * SPI + kk].y = __builtin_fma(gg * w[hy[kk]], w[ly[kk]], acc[gi * SPI + kk].y);
                 }
                 if (tid < d2) acc1[gi] = __builtin_fma(w[d2], w[tid], acc1[gi]);
             }
