@@ -335,7 +335,7 @@ def test_kalman_filter_sites_golden(amd):
     sites = GaussianSitesNat(dev(g["site_means"] / g["site_covs"][..., 0]), dev(-0.5 / g["site_covs"]))
     kf = KalmanFilterWithSites(ssm, EmissionModel(H), sites)
     np.testing.assert_allclose(float(kf.log_likelihood()), g["log_lik_total"], rtol=1e-7)
-    # the same through the fused entry point (time-invariant emission matrix declared: mfgm_kf_sites_loglik)
+    # the same through the fused entry point (time-invariant emission matrix declared: mfgm_kf_sites_elbo)
     kf2 = KalmanFilterWithSites(_gpu_ssm_from_golden(g, (), T), EmissionModel(H, constant_matrix=dev(g["H"])), sites)
     np.testing.assert_allclose(float(kf2.log_likelihood()), g["log_lik_total"], rtol=1e-7)
     post = kf.posterior_state_space_model()

@@ -59,6 +59,8 @@ class BaseKalmanFilter:
         ssm = self.prior_ssm
         R = self._r_inv
         o = R.shape[-1]
+        if R.dim() == 3 and ssm.B > 1 and R.shape[0] == ssm.B * ssm.T:      # one site per chain and time point, given flat [B T, o, o]
+            return R.reshape(ssm.B, ssm.T, o, o)
         return R.expand((ssm.B, ssm.T, o, o)) if R.dim() <= 3 else R.reshape(ssm.B, ssm.T, o, o)
 
     def _post_precision(self):
@@ -76,8 +78,10 @@ class BaseKalmanFilter:
         return torch.einsum("...ij,...ki,...k->...j", self._H(), self._rinv_full(), y)
 
     def _obs(self):
-        y = self.observations
-        return y.expand(self.prior_ssm.batch_shape + tuple(y.shape[-2:])).reshape((self.prior_ssm.B,) + tuple(y.shape[-2:]))
+        y, ssm = self.observations, self.prior_ssm
+        if y.dim() == 2 and ssm.B > 1 and y.shape[0] == ssm.B * ssm.T:       # flat [B T, o], as the sites are
+            return y.reshape(ssm.B, ssm.T, y.shape[-1])
+        return y.expand(ssm.batch_shape + tuple(y.shape[-2:])).reshape((ssm.B,) + tuple(y.shape[-2:]))
 
     def log_likelihood(self):
         """log p(obs) summed over the batch (kalman_filter.py:184-255)."""
@@ -260,7 +264,10 @@ class KalmanFilterWithSites(BaseKalmanFilter):
 
     @property
     def _log_det_observation_precision(self):
-        return linalg.logdet_spd(self._r_inv).sum(-1)
+        ld, ssm = linalg.logdet_spd(self._r_inv), self.prior_ssm
+        if ssm.B > 1 and ld.shape[0] == ssm.B * ssm.T:      # per-chain sites: one sum per chain, not the sum of all added to every chain
+            return ld.reshape(ssm.B, ssm.T).sum(-1)
+        return ld.sum(-1)
 
 
 class KalmanFilterWithSparseSites(BaseKalmanFilter):
