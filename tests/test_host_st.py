@@ -112,7 +112,7 @@ def test_projection_matches_the_reference_construction():
     (projection_inducing_states_to_observations, reference :494-507), to 1e-13."""
     from vidp_amd import kernels as K, space_kernels as SK
     from vidp_amd.likelihoods import Gaussian
-    from vidp_amd.sparse_pep import _cond_stats
+    from vidp_amd.conditionals import _cond_stats
     from vidp_amd.spatio_temporal_variational import SpatioTemporalSparseCVI
     rng = np.random.default_rng(3)
     for kt in (K.Matern12(0.7, 1.3), K.Matern32(1.5, 0.8), K.Matern52(1.1, 1.2)):

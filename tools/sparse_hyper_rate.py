@@ -55,6 +55,7 @@ def make(tag):
 
 def run_case(tag, cases, reps):
     from vidp_amd import hyper
+    from vidp_amd.conditionals import interval_gaps
     name, k, m, data = make(tag)
     d = k.state_dim
     pl = m.dist_p.plan
@@ -62,7 +63,7 @@ def run_case(tag, cases, reps):
     if "kernel" in cases:
         dd = m._data(data)
         marg = m._marginals()
-        _, glo, ghi = hyper.sparse_conditional_inputs(data[0], m.inducing_inputs)
+        _, glo, ghi = interval_gaps(data[0], m.inducing_inputs)
         fmu, fvar = m._predict_f_data(dd)
         g1, g2 = m.likelihood.ve_gradients_expectation(fmu, fvar, data[1])
         a = (g1 + 2.0 * g2 * fmu).reshape(-1).contiguous()

@@ -3,6 +3,8 @@ Host-side mirror of markovflow/conditionals.py: prediction between conditioning 
 `_conditional_statistics_from_transitions`, `conditional_predict`, `base_conditional_predict`, `pairwise_marginals`;
 conditionals.py:29-470).  Every query point is independent: these are batched d x d torch operations on the device,
 fed by the marginal / cross-covariance blocks of the HIP sweeps (factorisations and solves through vidp_amd.linalg).
+`interval_gaps`, `_cond_stats` (the statistics on either device) and `pair_moments` serve the models with sites on pairs of inducing
+states (pair_sites.py).
 """
 import torch
 
@@ -44,6 +46,28 @@ def _conditional_statistics(new_time_points, training_time_points, kernel):
     return torch.cat([F, G], dim=-1), T, idx
 
 
+def interval_gaps(time_points, inducing_points):
+    """(interval index, t - z-, z+ - t) of time points [N] among the inducing points [M], the ends padded with -+APPROX_INF."""
+    idx = torch.searchsorted(inducing_points.contiguous(), time_points.contiguous())
+    inf = APPROX_INF * torch.ones_like(inducing_points[-1:])
+    aug = torch.cat([-inf, inducing_points, inf])
+    return idx, time_points - aug[idx], aug[idx + 1] - time_points
+
+
+def _cond_stats(time_points, inducing_points, kernel):
+    """(P [N, d, 2d], T [N, d, d], interval [N]) as _conditional_statistics; on CPU tensors the same formulas through torch.linalg
+    (vidp_amd.linalg is device only)."""
+    if time_points.is_cuda:
+        return _conditional_statistics(time_points, inducing_points, kernel)
+    idx, gap_lo, gap_hi = interval_gaps(time_points, inducing_points)
+    A_mt, Q_mt = kernel.transition_statistics_local(gap_lo)
+    A_tp, Q_tp = kernel.transition_statistics_local(gap_hi)
+    AQ = A_tp @ Q_mt
+    sol = torch.linalg.solve(Q_tp + A_tp @ _T(AQ), AQ)
+    E = _T(sol)
+    return torch.cat([A_mt - E @ A_tp @ A_mt, E], dim=-1), Q_mt - _T(AQ) @ sol, idx
+
+
 def conditional_statistics(new_time_points, training_time_points, kernel):
     """conditionals.py:79-108."""
     P, T, _ = _conditional_statistics(new_time_points, training_time_points, kernel)
@@ -73,7 +97,12 @@ def conditional_predict(new_time_points, training_time_points, kernel, training_
 def pairwise_marginals(dist, initial_mean, initial_covariance):
     """Joint moments of every pair of subsequent states, padded with the prior at both ends (conditionals.py:424-470)."""
     means, covs = dist.marginals
-    sub = dist.subsequent_covariances()
+    return pair_moments(means, covs, dist.subsequent_covariances(), initial_mean, initial_covariance)
+
+
+def pair_moments(means, covs, sub, initial_mean, initial_covariance):
+    """The padding and pairing of pairwise_marginals on the blocks themselves: means [..., T, d], covs [..., T, d, d],
+    sub [..., T - 1, d, d] (Cov(x_t+1, x_t)) -> [..., T + 1, 2d], [..., T + 1, 2d, 2d]."""
     im = initial_mean.to(means.device).expand(means.shape[:-2] + (1, means.shape[-1]))
     ext_m = torch.cat([im, means, im], dim=-2)
     joint_mean = torch.cat([ext_m[..., :-1, :], ext_m[..., 1:, :]], dim=-1)

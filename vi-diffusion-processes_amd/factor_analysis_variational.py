@@ -15,7 +15,9 @@ Routes.  Device (sorted, un-batched time points on the GPU, P <= 64, Gaussian / 
 it): per step the parent's _marginals() (one factorisation, one selected inverse), one mfgm_fa_predict_lik cached on the sites' Stamp
 and one mfgm_fa_site_update[_q], so `update_sites; classic_elbo` costs one of each.  Torch (otherwise): materialised rows
 w_ip = sum_l W_ipl (h_i masked to latent l), the pair marginals, the likelihood classes' torch formulas and index_add_, a chunk of
-points at a time; on CPU tensors a dense posterior over all inducing states (small models, the host tests).
+points at a time; on CPU tensors a dense posterior over all inducing states (small models, the host tests; pair_sites.py).  The data
+cache, the site-update dispatch, the graph capture, the pair marginals and the KL term are DenseRouteSparseCVI's
+(sparse_variational_cvi.py).
 """
 import ctypes
 import math
@@ -24,13 +26,13 @@ import os
 import torch
 
 from . import _lib
+from .conditionals import _cond_stats
 from .kernels import FactorAnalysisKernel
 from .likelihoods import Bernoulli, Gaussian, Poisson
 from .packed import _ptr, _stream
-from .sparse_pep import _cond_stats
-from .sparse_variational_cvi import SparseCVIGaussianProcess
-from .spatio_temporal_variational import SpatioTemporalSparseCVI
-from .stamps import Stamp, wrote
+from .pair_sites import csr_offsets, initial_state, slot_mask
+from .sparse_variational_cvi import DenseRouteSparseCVI
+from .stamps import Stamp
 
 MAX_STATE_DIM = 32
 MAX_NATIVE_OUTPUTS = 64
@@ -46,7 +48,7 @@ def _tri_to_full(tri, L):
     return full
 
 
-class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
+class FactorAnalysisSparseCVI(DenseRouteSparseCVI):
     """kernel: a FactorAnalysisKernel (state_dim 2 .. 32); inducing_points [M] (sorted, one chain); likelihood: one Gaussian / Bernoulli /
     Poisson / ScalarQuadratureLikelihood for all outputs or a list of P of them.  Data: (time_points [N], observations [N, P]); a NaN
     observation marks a channel not observed at that time."""
@@ -71,16 +73,9 @@ class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
         super().__init__(kernel, inducing_points, likelihood, None, learning_rate)
         self._liks = liks
         self._dl = [int(k.state_dim) for k in kernel.kernels]
-        D, L = kernel.state_dim, kernel.latent_dim
-        mask = torch.zeros((L, 2 * D), dtype=torch.float64)
-        o = 0
-        for l, n in enumerate(self._dl):
-            mask[l, o:o + n] = 1.0
-            mask[l, D + o:D + o + n] = 1.0
-            o += n
         dev = inducing_points.device
         self._emission = kernel.latent_components._emission_matrix().to(dev, torch.float64)          # H_1 (+) ... (+) H_L  [L, D]
-        self._slot_mask = mask.to(dev)                                                              # [L, 2D]
+        self._slot_mask = slot_mask(self._dl, dev)                                                  # [L, 2D]
         # columns that share a likelihood object are evaluated in one call
         groups = {}
         for p, lk in enumerate(liks):
@@ -94,17 +89,6 @@ class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
     @property
     def output_dim(self):
         return self._kernel.output_dim
-
-    def _on_device(self):
-        return self.inducing_inputs.is_cuda
-
-    # the dense posterior over all inducing states (CPU tensors), the pair marginals of both routes and the KL term are those of the
-    # spatio-temporal model: functions of the kernel, the inducing points and the sites only
-    _dense_prior = SpatioTemporalSparseCVI._dense_prior
-    _dense_posterior = SpatioTemporalSparseCVI._dense_posterior
-    _pair_marginals = SpatioTemporalSparseCVI._pair_marginals
-    _kl = SpatioTemporalSparseCVI._kl
-    _need_device = SpatioTemporalSparseCVI._need_device
 
     def _native_kinds(self):
         """[(kind, param)] per output, or None when an output's likelihood has no native kind."""
@@ -138,18 +122,13 @@ class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
         t = input_data[0] if isinstance(input_data, (tuple, list)) else input_data
         return self._rows(self._weights(t), self._features(t)[0])
 
-    def _data(self, input_data):
-        """Constants of the device route (sorted times on the GPU): CSR offsets, h [N, 2D], c [N, L], W, the prior's initial state; None
-        where the torch route applies.  Kept until the time points or the loading matrix move."""
-        t = input_data[0]
-        c = getattr(self, "_data_cache", None)
-        if c is not None and c[0].matches(t, self._kernel.loading_version):
-            return c[1]
-        val = self._build_data(t)
-        self._data_cache = (Stamp(t, self._kernel.loading_version), val)
-        return val
+    @property
+    def _data_extra(self):
+        return (self._kernel.loading_version,)          # the constants hold W: kept until the time points or the loading matrix move
 
     def _build_data(self, t):
+        """Constants of the device route (sorted times on the GPU): CSR offsets, h [N, 2D], c [N, L], W, the prior's initial state; None
+        where the torch route applies."""
         z = self.inducing_inputs
         if not (t.dim() == 1 and t.is_cuda and z.is_cuda and os.environ.get("VIDP_NATIVE_FA", "1") != "0"
                 and self.output_dim <= MAX_NATIVE_OUTPUTS and self._native_kinds() is not None
@@ -163,10 +142,8 @@ class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
         else:
             mk = lambda *s: torch.zeros(s, dtype=torch.float64, device=z.device)
             h, cc, idx, W = mk(1, 2 * D), mk(1, L), torch.zeros(0, dtype=torch.int64, device=z.device), mk(P, L)
-        seg = torch.zeros(M + 2, dtype=torch.int32, device=z.device)
-        seg[1:] = torch.cumsum(torch.bincount(idx, minlength=M + 1), 0).to(torch.int32)
-        pm = self._kernel.initial_mean(()).to(z.device, torch.float64).contiguous()
-        pc = self._kernel.initial_covariance_matrix().to(z.device, torch.float64).contiguous()
+        seg = csr_offsets(idx, M + 1)
+        pm, pc = initial_state(self._kernel, z)
         sd = _lib.FaData()
         sd.M, sd.L, sd.P, sd.N = M, L, P, N
         for l, n in enumerate(self._dl):
@@ -220,17 +197,7 @@ class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
                                               _stream()), "mfgm_fa_predict_lik")
         return fmu, fvar, lmu, lcov
 
-    def _site_update(self, data, gam1, gam2, lr):
-        lib = self.dist_p.plan.lib
-        self._sync_sites()
-        st = ctypes.byref(data["struct"])
-        if self._packed:
-            _lib.check(lib.mfgm_fa_site_update_q(st, _ptr(gam1), _ptr(gam2), lr, _ptr(self._nat1), _ptr(self._nat2q), _stream()),
-                       "mfgm_fa_site_update_q")
-        else:
-            _lib.check(lib.mfgm_fa_site_update(st, _ptr(gam1), _ptr(gam2), lr, _ptr(self._nat1), _ptr(self._nat2), _stream()),
-                       "mfgm_fa_site_update")
-        self._sites_written()
+    _SITE_UPDATE = ("gam1", "gam2", "mfgm_fa_site_update", "mfgm_fa_site_update_q")      # gradients of _predict_lik; dense, packed entry
 
     def update_sites(self, input_data):
         """theta_m <- (1 - rho) theta_m + rho sum_{i in m} sum_p (g1_ip w_ip, g2_ip w_ip w_ip^T), dense across latents."""
@@ -238,39 +205,13 @@ class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
         if data is None:
             return self._update_sites_torch(input_data)
         r = self._predict_lik(data, input_data[1])
-        self._site_update(data, r["gam1"], r["gam2"], float(self.learning_rate))
+        g1, g2, dense, packed = self._SITE_UPDATE
+        self._site_update(data, r[g1], r[g2], float(self.learning_rate), dense, packed)
 
     def step_graph(self, input_data):
         """`update_sites(input_data); classic_elbo(input_data)` captured once in a HIP graph (device route): returns a callable that
         replays it and hands back the ELBO, a device scalar that every replay overwrites (as MultiLatentSparseCVI.step_graph)."""
-        data = self._data(input_data)
-        if data is None:
-            raise NotImplementedError("step_graph needs the device route: sorted, un-batched time points on the GPU")
-        # warm-up: every kernel of the step has run once (a site update at lr = 0 leaves the sites as they are), no state has moved
-        r = self._predict_lik(data, input_data[1])
-        self.classic_elbo(input_data)
-        self._site_update(data, r["gam1"], r["gam2"], 0.0)
-
-        def drop():
-            self._marg = self._fa_cache = self._kl_cache = None
-
-        drop()
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self.update_sites(input_data)
-            e = self.classic_elbo(input_data)
-        drop()                                       # nothing ran during the capture
-
-        def step():
-            graph.replay()
-            wrote(self._nat1, self._nat2q if self._packed else self._nat2)
-            self._sites_written()
-            self.dist_p.plan.epoch += 1
-            drop()
-            return e
-        step.graph = graph
-        return step
+        return self._step_graph(input_data, "_fa_cache")
 
     # ---- torch route (the correctness anchor) ----------------------------------------------------------------------------------------------
     def _rows(self, W, Hl):
@@ -353,15 +294,9 @@ class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
         return self._lik_terms(fmu, fvar, Y, grads=False)[0].sum()
 
     # ---- public interface ------------------------------------------------------------------------------------------------------------------
-    def _data_for(self, time_points):
-        c = getattr(self, "_data_cache", None)
-        if c is not None and c[0].matches(time_points, self._kernel.loading_version):
-            return c[1]
-        return self._build_data(time_points)
-
     def predict_f(self, time_points):
         """Marginal (means, variances) [N, P] of the P outputs at any time points."""
-        data = self._data_for(time_points)
+        data = self._data((time_points,), keep=False)
         if data is None:
             fmu, fvar = self._predict_torch(time_points)[:2]
             return fmu, fvar
@@ -373,7 +308,7 @@ class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
     def predict_latents(self, time_points, full_cov=False):
         """Marginal (means [N, L], variances [N, L]) of the L latent GPs at any time points; with full_cov the [N, L, L] covariance
         across latents (the mixing correlates them a posteriori)."""
-        data = self._data_for(time_points)
+        data = self._data((time_points,), keep=False)
         L = self.latent_dim
         if data is None:
             lmu, K = self._latents_torch(time_points)
@@ -457,14 +392,3 @@ class FactorAnalysisSparseCVI(SparseCVIGaussianProcess):
     def kernel_changed(self):
         super().kernel_changed()
         self._fa_cache = None
-
-    # ---- objects of the whole chain (device only) ------------------------------------------------------------------------------------------
-    @property
-    def dist_p(self):
-        self._need_device("dist_p")
-        return SparseCVIGaussianProcess.dist_p.fget(self)
-
-    @property
-    def dist_q(self):
-        self._need_device("dist_q")
-        return SparseCVIGaussianProcess.dist_q.fget(self)

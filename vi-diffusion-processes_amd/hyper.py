@@ -34,6 +34,7 @@ import torch
 
 from . import _lib, linalg
 from ._lib import FULL, SYM, VEC
+from .conditionals import interval_gaps
 
 _NO_SCORE = ("a HarmonicOscillator term without process noise has a transition that depends on its period but an exactly-zero Q: "
              "its likelihood has no score with respect to the period; set a jitter on the kernel")
@@ -198,15 +199,6 @@ def overlap_add(n1, n2):
     return lin, diag, sub
 
 
-def sparse_conditional_inputs(time_points, inducing):
-    """(interval index, t - z-, z+ - t) of sorted data points among the inducing points, the ends padded as the conditionals pad them."""
-    from .conditionals import APPROX_INF
-    idx = torch.searchsorted(inducing.contiguous(), time_points.contiguous())
-    inf = APPROX_INF * torch.ones_like(inducing[-1:])
-    aug = torch.cat([-inf, inducing, inf])
-    return idx, (time_points - aug[idx]).contiguous(), (aug[idx + 1] - time_points).contiguous()
-
-
 def conditional_part_torch(kernel, gap_lo, gap_hi, a, b, mu_pair, Sig_pair, idx, M):
     """Gradients of  sum_i a_i fmu_i + b_i fvar_i  at fixed pair moments through the conditionals, by autograd through kernel._parts:
     Q_mp = Q2 + A2 Q1 A2^T, x = Q_mp^-1 A2 Q1 h, y = h - A2^T x, w = (A1^T y, x), c = h^T Q1 y.  mu_pair [N, 2d], Sig_pair [N, 2d, 2d]:
@@ -302,7 +294,7 @@ def sparse_elbo_grad(model, input_data, parts=None):
     a, b = (g1 + 2.0 * g2 * fm).contiguous(), g2.contiguous()
     c = data.get("gaps") if data is not None else None
     if c is None:
-        c = sparse_conditional_inputs(time_points.reshape(-1), z)
+        c = interval_gaps(time_points.reshape(-1), z)
         if data is not None:
             data["gaps"] = c
     idx, gap_lo, gap_hi = c

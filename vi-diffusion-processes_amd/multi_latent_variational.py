@@ -13,7 +13,9 @@ Routes.  Device (sorted, un-batched time points on the GPU): per step one factor
 _marginals), one mfgm_ml_predict_lik (marginals of every latent, the likelihood, its gradients, the per-interval VE sums) and one
 mfgm_ml_site_update[_q]; the predict-lik result is cached on the sites' Stamp, so `update_sites; classic_elbo` costs one of each.
 Torch (VIDP_NATIVE_ML=0, CPU tensors or unsorted times): materialised rows W [N, L, 2D], the pair marginals, the likelihood classes'
-torch formulas and index_add_; on CPU tensors a dense posterior over all inducing states (small models, the host tests).
+torch formulas and index_add_; on CPU tensors a dense posterior over all inducing states (small models, the host tests;
+pair_sites.py).  The data cache, the site-update dispatch, the graph capture, the pair marginals and the KL term are
+DenseRouteSparseCVI's (sparse_variational_cvi.py).
 """
 import ctypes
 import os
@@ -21,17 +23,17 @@ import os
 import torch
 
 from . import _lib
+from .conditionals import _cond_stats
 from .kernels import IndependentMultiOutput, PiecewiseKernel
 from .packed import _ptr, _stream
-from .sparse_pep import _cond_stats
-from .sparse_variational_cvi import SparseCVIGaussianProcess
-from .spatio_temporal_variational import SpatioTemporalSparseCVI
-from .stamps import Stamp, wrote
+from .pair_sites import csr_offsets, initial_state, slot_mask
+from .sparse_variational_cvi import DenseRouteSparseCVI
+from .stamps import Stamp
 
 MAX_STATE_DIM = 32
 
 
-class MultiLatentSparseCVI(SparseCVIGaussianProcess):
+class MultiLatentSparseCVI(DenseRouteSparseCVI):
     """kernel: an IndependentMultiOutput whose output_dim equals likelihood.latent_dim (time-invariant emission, state_dim <= 32);
     inducing_points [M] (sorted, one chain); likelihood: MultiStageLikelihood or HeteroskedasticGaussian (vidp_amd.likelihoods).
     Data: (time_points [N], observations [N, 1])."""
@@ -60,30 +62,12 @@ class MultiLatentSparseCVI(SparseCVIGaussianProcess):
             raise NotImplementedError("the kernel's emission matrix must be time-invariant")
         super().__init__(kernel, inducing_points, likelihood, None, learning_rate)
         self._dl = [int(k.state_dim) for k in kernel.kernels]
-        D = kernel.state_dim
-        mask = torch.zeros((L, 2 * D), dtype=torch.float64)
-        o = 0
-        for l, n in enumerate(self._dl):
-            mask[l, o:o + n] = 1.0
-            mask[l, D + o:D + o + n] = 1.0
-            o += n
         self._emission = H.to(inducing_points.device, torch.float64)          # [L, D]
-        self._slot_mask = mask.to(inducing_points.device)                   # [L, 2D]: the slots of the pair that latent l owns
+        self._slot_mask = slot_mask(self._dl, inducing_points.device)       # [L, 2D]: the slots of the pair that latent l owns
 
     @property
     def latent_dim(self):
         return self._likelihood.latent_dim
-
-    def _on_device(self):
-        return self.inducing_inputs.is_cuda
-
-    # the dense posterior over all inducing states (CPU tensors), the pair marginals of both routes and the KL term are those of the
-    # spatio-temporal model: functions of the kernel, the inducing points and the sites only
-    _dense_prior = SpatioTemporalSparseCVI._dense_prior
-    _dense_posterior = SpatioTemporalSparseCVI._dense_posterior
-    _pair_marginals = SpatioTemporalSparseCVI._pair_marginals
-    _kl = SpatioTemporalSparseCVI._kl
-    _need_device = SpatioTemporalSparseCVI._need_device
 
     # ---- per-data-set constants ----------------------------------------------------------------------------------------------------------
     def _features(self, t):
@@ -101,18 +85,9 @@ class MultiLatentSparseCVI(SparseCVIGaussianProcess):
         t = input_data[0] if isinstance(input_data, (tuple, list)) else input_data
         return self._features(t)[0]
 
-    def _data(self, input_data):
+    def _build_data(self, t):
         """Constants of the device route (sorted times on the GPU): CSR offsets, h [N, 2D], c [N, L], the prior's initial state; None
         where the torch route applies."""
-        t = input_data[0]
-        c = getattr(self, "_data_cache", None)
-        if c is not None and c[0].matches(t):
-            return c[1]
-        val = self._build_data(t)
-        self._data_cache = (Stamp(t), val)
-        return val
-
-    def _build_data(self, t):
         z = self.inducing_inputs
         if not (t.dim() == 1 and t.is_cuda and z.is_cuda and os.environ.get("VIDP_NATIVE_ML", "1") != "0"
                 and (t.numel() < 2 or bool((t[1:] >= t[:-1]).all()))):
@@ -124,10 +99,8 @@ class MultiLatentSparseCVI(SparseCVIGaussianProcess):
         else:
             mk = lambda *s: torch.zeros(s, dtype=torch.float64, device=z.device)
             h, cc, idx = mk(1, 2 * D), mk(1, L), torch.zeros(0, dtype=torch.int64, device=z.device)
-        seg = torch.zeros(M + 2, dtype=torch.int32, device=z.device)
-        seg[1:] = torch.cumsum(torch.bincount(idx, minlength=M + 1), 0).to(torch.int32)
-        pm = self._kernel.initial_mean(()).to(z.device, torch.float64).contiguous()
-        pc = self._kernel.initial_covariance_matrix().to(z.device, torch.float64).contiguous()
+        seg = csr_offsets(idx, M + 1)
+        pm, pc = initial_state(self._kernel, z)
         sd = _lib.MlData()
         sd.M, sd.L, sd.N = M, L, N
         for l, n in enumerate(self._dl):
@@ -163,17 +136,7 @@ class MultiLatentSparseCVI(SparseCVIGaussianProcess):
         self._ml_cache = (self._key(), data, Stamp(Y), res)
         return res
 
-    def _site_update(self, data, g1, g2, lr):
-        lib = self.dist_p.plan.lib
-        self._sync_sites()
-        st = ctypes.byref(data["struct"])
-        if self._packed:
-            _lib.check(lib.mfgm_ml_site_update_q(st, _ptr(g1), _ptr(g2), lr, _ptr(self._nat1), _ptr(self._nat2q), _stream()),
-                       "mfgm_ml_site_update_q")
-        else:
-            _lib.check(lib.mfgm_ml_site_update(st, _ptr(g1), _ptr(g2), lr, _ptr(self._nat1), _ptr(self._nat2), _stream()),
-                       "mfgm_ml_site_update")
-        self._sites_written()
+    _SITE_UPDATE = ("g1", "g2", "mfgm_ml_site_update", "mfgm_ml_site_update_q")      # gradients of _predict_lik; dense, packed entry
 
     def update_sites(self, input_data):
         """theta_m <- (1 - rho) theta_m + rho sum_{i in m} (g1_i, g2_i projected through h_i), block-diagonal over latents."""
@@ -181,40 +144,13 @@ class MultiLatentSparseCVI(SparseCVIGaussianProcess):
         if data is None:
             return self._update_sites_torch(input_data)
         r = self._predict_lik(data, input_data[1])
-        self._site_update(data, r["g1"], r["g2"], float(self.learning_rate))
+        g1, g2, dense, packed = self._SITE_UPDATE
+        self._site_update(data, r[g1], r[g2], float(self.learning_rate), dense, packed)
 
     def step_graph(self, input_data):
         """`update_sites(input_data); classic_elbo(input_data)` captured once in a HIP graph (device route): returns a callable that
-        replays it and hands back the ELBO, a device scalar that every replay overwrites.  The site tensors and the sweep buffers keep
-        their addresses; a replay moves the sites behind the host's back, so it bumps their stamps and drops the cached results."""
-        data = self._data(input_data)
-        if data is None:
-            raise NotImplementedError("step_graph needs the device route: sorted, un-batched time points on the GPU")
-        # warm-up: every kernel of the step has run once (a site update at lr = 0 leaves the sites as they are), no state has moved
-        r = self._predict_lik(data, input_data[1])
-        self.classic_elbo(input_data)
-        self._site_update(data, r["g1"], r["g2"], 0.0)
-
-        def drop():
-            self._marg = self._ml_cache = self._kl_cache = None
-
-        drop()
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self.update_sites(input_data)
-            e = self.classic_elbo(input_data)
-        drop()                                       # nothing ran during the capture
-
-        def step():
-            graph.replay()
-            wrote(self._nat1, self._nat2q if self._packed else self._nat2)
-            self._sites_written()
-            self.dist_p.plan.epoch += 1
-            drop()
-            return e
-        step.graph = graph
-        return step
+        replays it and hands back the ELBO, a device scalar that every replay overwrites."""
+        return self._step_graph(input_data, "_ml_cache")
 
     # ---- torch route (the correctness anchor) ----------------------------------------------------------------------------------------------
     def _predict_torch(self, t):
@@ -244,11 +180,7 @@ class MultiLatentSparseCVI(SparseCVIGaussianProcess):
     # ---- public interface ------------------------------------------------------------------------------------------------------------------
     def predict_f(self, time_points):
         """Marginal (means, variances) [N, L] of the L latents at any time points."""
-        c = getattr(self, "_data_cache", None)
-        if c is not None and c[0].matches(time_points):
-            data = c[1]
-        else:
-            data = self._build_data(time_points)
+        data = self._data((time_points,), keep=False)
         if data is None:
             fmu, fvar, _, _ = self._predict_torch(time_points)
             return fmu, fvar
@@ -291,14 +223,3 @@ class MultiLatentSparseCVI(SparseCVIGaussianProcess):
         """Forwards to the likelihood (which raises for both multi-latent likelihoods, as in the reference)."""
         t, Y = input_data
         return self._likelihood.predict_log_density(*self.predict_f(t), Y)
-
-    # ---- objects of the whole chain (device only) ------------------------------------------------------------------------------------------
-    @property
-    def dist_p(self):
-        self._need_device("dist_p")
-        return SparseCVIGaussianProcess.dist_p.fget(self)
-
-    @property
-    def dist_q(self):
-        self._need_device("dist_q")
-        return SparseCVIGaussianProcess.dist_q.fget(self)

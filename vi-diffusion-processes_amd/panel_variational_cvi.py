@@ -13,6 +13,8 @@ gradients, per-series VE sums) -> mfgm_panel_site_update; the predict pass is ca
 serves the update of the next.  Torch (anything else: d > 8, an LEG kernel, any other ScalarQuadratureLikelihood, VIDP_NATIVE_PANEL=0,
 CPU tensors): the same quantities with batched torch ops -- on the device around the same factorisation and selected inverse, on CPU
 tensors around a dense posterior over all inducing states of every series (small models, the host tests); the correctness anchor.
+The dense posterior, the pair marginals and the KL term are the functions of pair_sites.py, which the single-chain models call
+without the batch axis.
 """
 import ctypes
 import os
@@ -21,11 +23,11 @@ import torch
 
 from . import _lib
 from ._lib import FULL, SYM, VEC
+from .conditionals import _cond_stats
 from .kernels import LatentExponentiallyGenerated, PiecewiseKernel
 from .likelihoods import Bernoulli, Gaussian, Poisson
 from .packed import _ptr, _stream
-from .sparse_pep import _cond_stats
-from .spatio_temporal_variational import SpatioTemporalSparseCVI
+from .pair_sites import chain_kl, csr_offsets, dense_kl, initial_state, need_device, on_device, pair_marginals
 from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
 from .stamps import Stamp
 
@@ -103,16 +105,10 @@ class PanelSparseCVI:
         return self._likelihood
 
     # ---- routes ----------------------------------------------------------------------------------------------------------------------------
-    def _on_device(self):
-        return self.inducing_inputs.is_cuda
-
     def _native(self):
-        return (self._on_device() and self._kernel.state_dim <= 8 and type(self._likelihood) in _KINDS
+        return (on_device(self) and self._kernel.state_dim <= 8 and type(self._likelihood) in _KINDS
                 and not _has_kernel(self._kernel, LatentExponentiallyGenerated) and os.environ.get("VIDP_NATIVE_PANEL", "1") != "0"
                 and self._nat1.is_contiguous() and self._nat2.is_contiguous())
-
-    _dense_prior = SpatioTemporalSparseCVI._dense_prior
-    _need_device = SpatioTemporalSparseCVI._need_device
 
     # ---- per-data-set constants ------------------------------------------------------------------------------------------------------------
     def _features(self, t, need_sorted):
@@ -142,15 +138,11 @@ class PanelSparseCVI:
             mk = lambda *s: torch.zeros(s, dtype=torch.float64, device=z.device)
             w, c, idx = mk(B, 0, 2 * d), mk(B, 0), torch.zeros((B, 0), dtype=torch.int64, device=z.device)
         f = dict(w=w, c=c, idx=idx, n=n, sorted=is_sorted)
-        if self._on_device():
+        if on_device(self):
             f["idx32"] = idx.to(torch.int32).contiguous()
             if is_sorted:
-                cnt = torch.zeros((B, M + 1), dtype=torch.int64, device=z.device).scatter_add_(1, idx, torch.ones_like(idx))
-                seg = torch.zeros((B, M + 2), dtype=torch.int32, device=z.device)
-                seg[:, 1:] = torch.cumsum(cnt, 1).to(torch.int32)
-                f["seg"] = seg
-            f["pm"] = self._kernel.initial_mean(()).to(z.device, torch.float64).contiguous()
-            f["pc"] = self._kernel.initial_covariance(z[:1]).to(z.device, torch.float64).contiguous()
+                f["seg"] = csr_offsets(idx, M + 1)
+            f["pm"], f["pc"] = initial_state(self._kernel, z)
             sd = _lib.PanelData()
             sd.B, sd.M, sd.d, sd.N = B, M, d, n
             sd.idx, sd.seg = f["idx32"].data_ptr(), (f["seg"].data_ptr() if is_sorted else None)
@@ -186,7 +178,7 @@ class PanelSparseCVI:
     @property
     def dist_p(self):
         """The prior of the B series at the inducing points: a batch-B StateSpaceModel (the same chain B times)."""
-        self._need_device("dist_p")
+        need_device(self, "dist_p")
         if self._dist_p is None:
             z = self.inducing_inputs
             self._dist_p = self._kernel.state_space_model(z[None].expand(self.num_series, -1).contiguous())
@@ -241,65 +233,18 @@ class PanelSparseCVI:
         self._marg = dict(version=self._key(), packed=s, logdetL=f["logdet"])
         return self._marg
 
-    def _dense_posterior(self):
-        """CPU tensors: (precision [B, Md, Md], mean [B, Md], covariance [B, Md, Md]) of all inducing states of every series."""
-        c = getattr(self, "_dense_q", None)
-        if c is not None and self._current(c[0]):
-            return c[1]
-        B, d, M = self.num_series, self._kernel.state_dim, int(self.inducing_inputs.shape[0])
-        b = torch.zeros((B, (M + 2) * d), dtype=torch.float64)
-        Q = torch.zeros((B, (M + 2) * d, (M + 2) * d), dtype=torch.float64)
-        for m in range(M + 1):
-            sl = slice(m * d, (m + 2) * d)
-            b[:, sl] += self._nat1[:, m]
-            Q[:, sl, sl] += -2.0 * self._nat2[:, m]
-        P = self._dense_prior()["P"] + Q[:, d:-d, d:-d]
-        S = torch.linalg.inv(P)
-        val = (P, (S @ b[:, d:-d, None])[..., 0], S)
-        self._dense_q = (self._key(), val)
-        return val
-
-    def _pair_marginals(self):
-        """Means [B, M + 1, 2d] and covariances [B, M + 1, 2d, 2d] of the pairs of consecutive inducing states of every series, the
-        prior's initial state at both ends (torch route)."""
-        B, d, M = self.num_series, self._kernel.state_dim, int(self.inducing_inputs.shape[0])
-        if self._on_device():
-            pl, s = self.dist_p.plan, self._marginals()["packed"]
-            mu, Sig, Sub = pl.unpack(VEC, s["x"]), pl.unpack(SYM, s["Sig"]), pl.unpack(FULL, s["Sub"], M - 1)
-        else:
-            _, mq, S = self._dense_posterior()
-            mu, blk, ar = mq.view(B, M, d), S.view(B, M, d, M, d), torch.arange(M)
-            Sig, Sub = blk[:, ar, :, ar, :].transpose(0, 1), blk[:, ar[1:], :, ar[:-1], :].transpose(0, 1)
-        dev = mu.device
-        pm = self._kernel.initial_mean(()).to(dev, torch.float64).expand(B, 1, d)
-        pc = self._kernel.initial_covariance_matrix().to(dev, torch.float64).expand(B, 1, d, d)
-        em, ec = torch.cat([pm, mu, pm], 1), torch.cat([pc, Sig, pc], 1)
-        zero = torch.zeros_like(pc)
-        es = torch.cat([zero, Sub, zero], 1)
-        top = torch.cat([ec[:, :-1], es.transpose(-1, -2)], -1)
-        bot = torch.cat([es, ec[:, 1:]], -1)
-        return torch.cat([em[:, :-1], em[:, 1:]], -1), torch.cat([top, bot], -2)
-
-    def _kl(self):
-        """KL[q_b || p] per series, [B]."""
-        if not self._on_device():
-            pr = self._dense_prior()
-            P, mq, S = self._dense_posterior()
-            n = mq.shape[-1]
-            return 0.5 * ((pr["P"] * S).sum((-1, -2)) + torch.einsum("bi,ij,bj->b", mq, pr["P"], mq) - n - pr["logdet"]
-                          + torch.linalg.slogdet(P)[1])
-        m, pn, p = self._marginals(), self._prior_natural(), self.dist_p
-        s = m["packed"]
-        tr, mh = p.plan.kl_terms(s["Sig"], s["Sub"], s["x"], pn["nat"]["diag"], pn["nat"]["sub"], pn["mean"], aD=-2.0, aS=-1.0)
-        return 0.5 * (tr + mh - float(p.T * p.d) + 2.0 * pn["nat"]["sumlogchol"] + 2.0 * m["logdetL"])
-
     # ---- the predict pass ------------------------------------------------------------------------------------------------------------------
     def _rows(self, n):
         return max(1, self.CHUNK // max(n, 1))
 
     def _predict_torch(self, f):
-        """(fmu, fvar) [B, n] at the points of `f` from the pair marginals, with batched torch ops."""
-        pm, pc = self._pair_marginals()
+        """(fmu, fvar) [B, n] at the points of `f` with batched torch ops, from the pair marginals of every series [B, M + 1, 2d],
+        [B, M + 1, 2d, 2d]: those of the device sweeps, or on CPU tensors of the dense posterior (pair_sites.py)."""
+        blocks = None
+        if on_device(self):
+            pl, s = self.dist_p.plan, self._marginals()["packed"]
+            blocks = pl.unpack(VEC, s["x"]), pl.unpack(SYM, s["Sig"]), pl.unpack(FULL, s["Sub"], pl.T - 1)
+        pm, pc = pair_marginals(self, blocks)
         w, idx = f["w"], f["idx"]
         fmu, fvar = torch.empty_like(f["c"]), f["c"].clone()
         for lo in range(0, self.num_series, self._rows(f["n"])):          # the pair covariances are gathered a block of series at a time
@@ -372,7 +317,11 @@ class PanelSparseCVI:
 
     def elbo_per_series(self, input_data):
         """[B]: sum_i E_q log p(y_bi | f_bi) - KL[q_b(s_Z) || p(s_Z)] of every series."""
-        return self._predict_lik(input_data)["ve_series"] - self._kl()
+        ve = self._predict_lik(input_data)["ve_series"]
+        if not on_device(self):
+            return ve - dense_kl(self)
+        pn = self._prior_natural()
+        return ve - chain_kl(self.dist_p, self._marginals(), pn, pn["mean"])
 
     def classic_elbo(self, input_data):
         """The bound of the panel: the sum of elbo_per_series, a scalar."""

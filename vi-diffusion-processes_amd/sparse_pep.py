@@ -27,27 +27,12 @@ import math
 import torch
 
 from . import _lib
-from .conditionals import _conditional_statistics, base_conditional_predict
+from .conditionals import _cond_stats, base_conditional_predict
 from .packed import _ptr, _stream
+from .pair_sites import dense_posterior, dense_prior, on_device
 from .pep import gradient_correction
-from .sparse_variational_cvi import SparseCVIGaussianProcess
+from .sparse_variational_cvi import DenseRouteSparseCVI
 from .stamps import wrote
-
-
-def _cond_stats(time_points, inducing_points, kernel):
-    """(P [N, d, 2d], T [N, d, d], interval [N]) as conditionals._conditional_statistics; on CPU tensors the same formulas through
-    torch.linalg (vidp_amd.linalg is device only)."""
-    if time_points.is_cuda:
-        return _conditional_statistics(time_points, inducing_points, kernel)
-    idx = torch.searchsorted(inducing_points.contiguous(), time_points.contiguous())
-    inf = 1e10 * torch.ones_like(inducing_points[-1:])
-    aug = torch.cat([-inf, inducing_points, inf])
-    A_mt, Q_mt = kernel.transition_statistics_local(time_points - aug[idx])
-    A_tp, Q_tp = kernel.transition_statistics_local(aug[idx + 1] - time_points)
-    AQ = A_tp @ Q_mt
-    sol = torch.linalg.solve(Q_tp + A_tp @ AQ.transpose(-1, -2), AQ)
-    E = sol.transpose(-1, -2)
-    return torch.cat([A_mt - E @ A_tp @ A_mt, E], dim=-1), Q_mt - AQ.transpose(-1, -2) @ sol, idx
 
 
 def _chol_parts(A):
@@ -108,12 +93,13 @@ def interval_update(likelihood, alpha, lr, idx, w, c, y, mu, S, nat1, nat2, lnor
             torch.where(ok, e, torch.full_like(e, float("nan"))), skipped.to(torch.int32))
 
 
-class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
+class SparsePowerExpectationPropagation(DenseRouteSparseCVI):
     """sparse_pep.py:41-559.  One chain: inducing points [M]; sites nat1 [M+1, 2d], nat2 [M+1, 2d, 2d], log_norm [M+1, 1].
     The sites are public and assignable; every nat2_m must be symmetric (the kernel reads its lower triangle, the torch route the whole
     matrix).  `mean_function` is accepted for the reference's signature and ignored here (SparseCVIGaussianProcess itself applies it).
     `likelihood` is a PEP wrapper (PEPScalarLikelihood / PEPGaussian); classic_elbo and predict_log_density use the likelihood it wraps.
-    On CPU tensors the posterior comes from a dense (M d) x (M d) inverse: that route exists for small models and the host tests only."""
+    On CPU tensors the posterior comes from a dense (M d) x (M d) inverse (pair_sites.py): that route exists for small models and the
+    host tests only."""
 
     def __init__(self, kernel, inducing_points, likelihood, mean_function=None, learning_rate=1.0, alpha=1.0):
         if not 0.0 < float(alpha) <= 1.0:
@@ -168,92 +154,16 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
         return self.fraction_sites(time_points)[self._indices(time_points)]
 
     # ---- posterior ------------------------------------------------------------------------------------------------------------------
-    def _on_device(self):
-        return self.inducing_inputs.is_cuda
-
-    def _dense_prior(self):
-        """CPU tensors (small models only): the prior precision over all inducing states as one dense matrix, its log determinant, P0."""
-        c = getattr(self, "_dense_p", None)
-        if c is None:
-            z, d = self.inducing_inputs, self._kernel.state_dim
-            M = z.shape[0]
-            A, Q = self._kernel.transition_statistics_local(z[1:] - z[:-1])
-            P0 = self._kernel.initial_covariance_matrix().to(z.device, torch.float64)
-            Qi = torch.linalg.inv(Q)
-            P = torch.zeros((M * d, M * d), dtype=torch.float64, device=z.device)
-            P[:d, :d] = torch.linalg.inv(P0)
-            for t in range(M - 1):
-                a, b = slice(t * d, (t + 1) * d), slice((t + 1) * d, (t + 2) * d)
-                QA = Qi[t] @ A[t]
-                P[a, a] += A[t].T @ QA
-                P[b, b] += Qi[t]
-                P[b, a] -= QA
-                P[a, b] -= QA.T
-            c = self._dense_p = dict(P=P, logdet=torch.linalg.slogdet(P)[1], P0=P0)
-        return c
-
-    def _dense_posterior(self, nat1=None, nat2=None):
-        """CPU tensors (small models only): (Lambda_q, mu_q, Sigma_q) with the sites overlap-added densely."""
-        nat1 = self.nat1 if nat1 is None else nat1
-        nat2 = self.nat2 if nat2 is None else nat2
-        d = self._kernel.state_dim
-        M = self.inducing_inputs.shape[0]
-        b = torch.zeros((M + 2) * d, dtype=torch.float64)
-        Q = torch.zeros(((M + 2) * d, (M + 2) * d), dtype=torch.float64)
-        for m in range(M + 1):
-            sl = slice(m * d, (m + 2) * d)
-            b[sl] += nat1[m]
-            Q[sl, sl] += -2.0 * nat2[m]
-        P = self._dense_prior()["P"] + Q[d:-d, d:-d]
-        S = torch.linalg.inv(P)
-        return P, S @ b[d:-d], S
-
     def compute_posterior_ssm(self, nat1, nat2):
         """The posterior over the inducing states for the given sites, as a StateSpaceModel (sparse_pep.py:197-231)."""
-        if not self._on_device():
+        if not on_device(self):
             raise NotImplementedError("the posterior state-space model needs the sites on the device")
-        from ._lib import FULL, SYM, VEC
-        from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
-        p = self.dist_p
-        pl, T, d = p.plan, p.T, p.d
-        pn = self._prior_natural()
-        n1, n2 = nat1.contiguous(), nat2.contiguous()
-        lin, diag, sub = (torch.empty(shape, dtype=torch.float64, device=pl.device) for shape in ((T, d), (T, d, d), (T, d, d)))
-        _lib.check(pl.lib.mfgm_sparse_theta(T, d, _ptr(n1), _ptr(n2), _ptr(pn["lin"]), _ptr(pn["diag"]), _ptr(pn["sub"]), _ptr(lin),
-                                            _ptr(diag), _ptr(sub), _stream()), "mfgm_sparse_theta")
-        if pl.d > 8:
-            packed = (lin.view(-1), diag.view(-1), sub.view(-1))
-        else:
-            packed = (pl.pack(VEC, lin[None]), pl.pack(SYM, diag[None]),
-                      pl.pack(FULL, sub[None, :T - 1].contiguous()) if T > 1 else pl.zeros(FULL))
-        q = naturals_to_ssm_params_packed(pl, *packed)
-        q.batch_shape = p.batch_shape
-        return q
+        return self._posterior_ssm(nat1.contiguous(), nat2.contiguous())
 
     def compute_marginals(self):
         """Pairwise marginals (means [M+1, 2d], covariances [M+1, 2d, 2d]) of the posterior, the prior's initial state at both ends
         (sparse_pep.py:240-249)."""
-        d = self._kernel.state_dim
-        if self._on_device():
-            m = self._marginals()
-            mu, Sig, Sub = m["mu"], m["Sig"], m["Sub"][:-1]
-        else:
-            _, mq, S = self._dense_posterior()
-            M = self.inducing_inputs.shape[0]
-            mu = mq.view(M, d)
-            blk = S.view(M, d, M, d)
-            ar = torch.arange(M)
-            Sig, Sub = blk[ar, :, ar, :], blk[ar[1:], :, ar[:-1], :]
-        dev = mu.device
-        pm = self._kernel.initial_mean(()).to(dev, torch.float64)[None]
-        pc = self._kernel.initial_covariance_matrix().to(dev, torch.float64)[None]
-        em = torch.cat([pm, mu, pm], 0)
-        ec = torch.cat([pc, Sig, pc], 0)
-        zero = torch.zeros_like(pc)
-        es = torch.cat([zero, Sub, zero], 0)
-        top = torch.cat([ec[:-1], es.transpose(-1, -2)], -1)
-        bot = torch.cat([es, ec[1:]], -1)
-        return torch.cat([em[:-1], em[1:]], -1), torch.cat([top, bot], -2)
+        return self._pair_marginals()
 
     # ---- the reference's per-point inspection helpers (they gather) ------------------------------------------------------------------
     def remove_cavity_from_marginals(self, time_points, marginals):
@@ -321,7 +231,7 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
 
     def compute_log_norm(self, input_data):
         """sum_{i in m} e_i per interval, [M + 1]: e_i = log Z_i + g_c - g_q at the cavity of the interval (NaN where it is improper)."""
-        data = self._data(input_data) if self._on_device() else None
+        data = self._data(input_data) if on_device(self) else None
         if self._native(data):
             e = torch.empty(self.inducing_inputs.shape[0] + 1, dtype=torch.float64, device=self.inducing_inputs.device)
             self._launch(data, input_data[1], 0.0, None, e, None)
@@ -331,7 +241,7 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
     def update_sites(self, input_data):
         """One damped PEP update of every site: X_m <- (1 - lr) X_m + lr ((1 - alpha) X_m + sum_{i in m} dX_i) for X = (nat1, nat2,
         log_norm) (sparse_pep.py:473-487)."""
-        data = self._data(input_data) if self._on_device() else None
+        data = self._data(input_data) if on_device(self) else None
         if self._native(data):
             self._launch(data, input_data[1], self.learning_rate, self.log_norm, None, self.skipped)
             wrote(self.log_norm)
@@ -345,10 +255,10 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
     # ---- objectives -----------------------------------------------------------------------------------------------------------------
     def _dist_p_normalizer(self):
         if self._norm_p is None:                     # the prior is fixed
-            if self._on_device():
+            if on_device(self):
                 self._norm_p = self.dist_p.normalizer().reshape(())
             else:
-                p = self._dense_prior()
+                p = dense_prior(self)
                 self._norm_p = 0.5 * (p["P"].shape[0] * math.log(2.0 * math.pi) - p["logdet"])
         return self._norm_p
 
@@ -356,8 +266,8 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
         """dist_q.normalizer() = 1/2 (dim log 2 pi - log det Lambda_q + mu_q^T Lambda_q mu_q) without building dist_q and without a
         factorisation of its own: the cached marginals hold log|L| = 1/2 log det Lambda_q and mu_q, and Lambda_q mu_q is the posterior's
         linear natural parameter, the prior's plus the overlap-added nat1 (the packed sites are not unpacked)."""
-        if not self._on_device():
-            P, mu, _ = self._dense_posterior()
+        if not on_device(self):
+            P, mu, _ = dense_posterior(self)
             return 0.5 * (P.shape[0] * math.log(2.0 * math.pi) - torch.linalg.slogdet(P)[1] + mu @ P @ mu)
         p = self.dist_p
         d = p.d
@@ -378,15 +288,15 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
     def classic_elbo(self, input_data):
         """sum_i E_q log p(y_i | f_i) - KL[q(u) || p(u)] (sparse_pep.py:520-542), with the wrapped likelihood's variational
         expectations."""
-        if self._on_device():
+        if on_device(self):
             return super().classic_elbo(input_data)
         idx, w, c, y = self._torch_terms(input_data)
         mu, S = self.compute_marginals()
         fmu = (w * mu[idx]).sum(-1)
         fvar = torch.einsum("pi,pij,pj->p", w, S[idx], w) + c
         ve = self._likelihood.variational_expectations(fmu[:, None], fvar[:, None], y[:, None]).sum()
-        P, mq, Sq = self._dense_posterior()
-        p = self._dense_prior()
+        P, mq, Sq = dense_posterior(self)
+        p = dense_prior(self)
         kl = 0.5 * ((p["P"] * Sq).sum() + mq @ p["P"] @ mq - P.shape[0] - p["logdet"] - torch.linalg.slogdet(Sq)[1])
         return ve - kl
 
@@ -398,6 +308,6 @@ class SparsePowerExpectationPropagation(SparseCVIGaussianProcess):
 
     @property
     def posterior(self):
-        if not self._on_device():
+        if not on_device(self):
             raise NotImplementedError("the posterior process needs the sites on the device")
         return super().posterior

@@ -3,6 +3,8 @@ Host-side mirror of markovflow/models/sparse_variational_cvi.py `SparseCVIGaussi
 (sparse_variational_cvi.py:38-292): CVI with sites on pairs of consecutive inducing states.  The overlap-add of the
 [M+1, 2d, 2d] sites into the block-tri-diagonal natural parameters and the data -> site segment sums (a Python list of
 M+1 reduce_sums in the reference, :199-213) are single index_add operations; the posterior refresh runs in the HIP sweeps.
+`DenseRouteSparseCVI` below it is the parent of the models built on it (sparse_pep.py, spatio_temporal_variational.py,
+multi_latent_variational.py, factor_analysis_variational.py): what they share beyond the plain model.
 """
 import ctypes
 import os
@@ -13,9 +15,10 @@ from . import _lib
 from ._lib import FULL, SYM, VEC
 from .conditionals import _conditional_statistics, conditional_statistics
 from .packed import Plan, _ptr, _stream
+from .pair_sites import chain_kl, csr_offsets, dense_kl, initial_state, need_device, on_device, pair_marginals
 from .posterior import ConditionalProcess
 from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
-from .stamps import Stamp
+from .stamps import Stamp, wrote
 from .variational_cvi import back_project_nats
 
 
@@ -153,7 +156,12 @@ class SparseCVIGaussianProcess:
         p = self.dist_p
         if self._shard is not None:
             self._gather_sites()
-        lin, diag, sub = (x.clone() for x in self._theta())      # _theta() reuses its buffers
+        return self._posterior_ssm()
+
+    def _posterior_ssm(self, nat1=None, nat2=None):
+        """The posterior over the inducing states for the given sites (the model's own by default) as a StateSpaceModel."""
+        p = self.dist_p
+        lin, diag, sub = (x.clone() for x in self._theta(nat1, nat2))      # _theta() reuses its buffers
         q = naturals_to_ssm_params_packed(p.plan, lin, diag, sub)
         q.batch_shape = p.batch_shape
         return q
@@ -167,14 +175,25 @@ class SparseCVIGaussianProcess:
         return obj, self._likelihood.ve_gradients_expectation(Fmu, Fvar, Y)
 
     # ---- fused route (csrc/mfgm_sparse.h): sorted data points, one chain ---------------------------------------------------------------
-    def _data(self, input_data):
-        """Per-data-set constants of the fused route: CSR offsets of the data points per inter-inducing interval, w_i = H P_i, c_i = H T_i H^T
-        (conditionals.py:207-256: functions of the time points and the kernel only), the kernel's initial state; or None when the
-        route does not apply (unsorted or batched time points)."""
-        time_points, observations = input_data
+    _data_extra = ()          # what a data set's constants depend on besides the inputs: more parts of the stamp they are kept under
+
+    def _data(self, input_data, keep=True):
+        """Per-data-set constants of the device route (_build_data of the inputs, input_data[0]), or None where the route does not
+        apply; kept until the inputs move.  keep=False (other inputs, as prediction points): the kept set serves when it is the one
+        asked for, nothing is stored."""
+        x = input_data[0]
         c = getattr(self, "_data_cache", None)
-        if c is not None and c[0].matches(time_points):
+        if c is not None and c[0].matches(x, *self._data_extra):
             return c[1]
+        val = self._build_data(x)
+        if keep:
+            self._data_cache = (Stamp(x, *self._data_extra), val)
+        return val
+
+    def _build_data(self, time_points):
+        """The constants of the fused route, uncached: CSR offsets of the data points per inter-inducing interval, w_i = H P_i,
+        c_i = H T_i H^T (conditionals.py:207-256: functions of the time points and the kernel only), the kernel's initial state; or None
+        when the route does not apply (unsorted or batched time points)."""
         val = None
         z = self.inducing_inputs
         if (time_points.dim() == 1 and z.dim() == 1 and time_points.is_cuda and os.environ.get("VIDP_FUSED_SPARSE", "1") != "0"
@@ -197,17 +216,14 @@ class SparseCVIGaussianProcess:
             else:
                 idx = torch.zeros(0, dtype=torch.int64, device=z.device)
                 w, cc = (torch.zeros((1, 2 * d), dtype=torch.float64, device=z.device), torch.zeros(1, dtype=torch.float64, device=z.device))
-            seg = torch.zeros(m_hi - m_lo + 1, dtype=torch.int32, device=z.device)
-            seg[1:] = torch.cumsum(torch.bincount(idx - m_lo, minlength=m_hi - m_lo), 0).to(torch.int32)
-            pm = self._kernel.initial_mean(()).to(z.device, torch.float64).contiguous()
-            pc = self._kernel.initial_covariance(z[:1]).to(z.device, torch.float64).contiguous()
+            seg = csr_offsets(idx - m_lo, m_hi - m_lo)
+            pm, pc = initial_state(self._kernel, z)
             sd = _lib.SparseData()
             sd.M, sd.d, sd.N, sd.m_lo, sd.m_hi = M, d, N, m_lo, m_hi
             sd.seg, sd.w, sd.c, sd.prior_mean, sd.prior_cov = seg.data_ptr(), w.data_ptr(), cc.data_ptr(), pm.data_ptr(), pc.data_ptr()
             val = dict(struct=sd, keep=(seg, w, cc, pm, pc), N=N, own=own, t=time_points)
         if val is None and self._shard is not None:
             raise ValueError("a shared chain needs sorted, un-batched time points on the device")
-        self._data_cache = (Stamp(input_data[0]), val)
         return val
 
     def _prior_natural(self):
@@ -268,8 +284,11 @@ class SparseCVIGaussianProcess:
         return (self._inverse_form() and os.environ.get("VIDP_FUSED_THETA", "1") != "0" and self.nat1.is_contiguous()
                 and (self._packed or self.nat2.is_contiguous()))
 
-    def _theta(self):
-        """Posterior naturals of the current sites, packed (lin, diag, sub): one pass over the sites (mfgm_sparse_theta)."""
+    def _theta(self, nat1=None, nat2=None):
+        """Posterior naturals of the given sites (dense, contiguous; the model's own by default), packed (lin, diag, sub): one pass over
+        the sites (mfgm_sparse_theta)."""
+        nat1 = self.nat1 if nat1 is None else nat1
+        nat2 = self.nat2 if nat2 is None else nat2
         p = self.dist_p
         pl, T, d = p.plan, p.T, p.d
         pn = self._prior_natural()
@@ -278,7 +297,7 @@ class SparseCVIGaussianProcess:
         if not b:
             mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=pl.device)
             b.update(lin=mk(T, d), diag=mk(T, d, d), sub=mk(T, d, d))
-        _lib.check(pl.lib.mfgm_sparse_theta(T, d, _ptr(self.nat1), _ptr(self.nat2), _ptr(pn["lin"]), _ptr(pn["diag"]), _ptr(pn["sub"]),
+        _lib.check(pl.lib.mfgm_sparse_theta(T, d, _ptr(nat1), _ptr(nat2), _ptr(pn["lin"]), _ptr(pn["diag"]), _ptr(pn["sub"]),
                                             _ptr(b["lin"]), _ptr(b["diag"]), _ptr(b["sub"]), _stream()), "mfgm_sparse_theta")
         if wide:
             return b["lin"].view(-1), b["diag"].view(-1), b["sub"].view(-1)
@@ -527,3 +546,78 @@ class SparseCVIGaussianProcess:
         X, Y = input_data
         f_mean, f_var = self.posterior.predict_f(X, full_output_cov=full_output_cov)
         return self._likelihood.predict_log_density(f_mean, f_var, Y)
+
+
+class DenseRouteSparseCVI(SparseCVIGaussianProcess):
+    """SparseCVIGaussianProcess plus what the models built on it share (sparse Power EP, the spatio-temporal, multi-latent and
+    factor-analysis models).  On CPU tensors the posterior comes from a dense (M d) x (M d) inverse (pair_sites.py: small models, the
+    host tests), so the objects of the whole chain need the device; on the device the pair marginals and the KL term come from the
+    parent's cached marginals.  One chain: inducing points [M]."""
+
+    @property
+    def dist_p(self):
+        need_device(self, "dist_p")
+        return SparseCVIGaussianProcess.dist_p.fget(self)
+
+    @property
+    def dist_q(self):
+        need_device(self, "dist_q")
+        return SparseCVIGaussianProcess.dist_q.fget(self)
+
+    def _pair_marginals(self):
+        """Means [M + 1, 2D] and covariances [M + 1, 2D, 2D] of the pairs of consecutive inducing states (pair_sites.pair_marginals)."""
+        if not on_device(self):
+            return pair_marginals(self)
+        m = self._marginals()
+        return pair_marginals(self, (m["mu"], m["Sig"], m["Sub"][:-1]))
+
+    def _kl(self):
+        """KL[q(s_Z) || p(s_Z)]."""
+        if not on_device(self):
+            return dense_kl(self)
+        return chain_kl(self.dist_p, self._marginals(), self._prior_natural(), self._prior_mean_packed()).sum()
+
+    def _site_update(self, data, g1, g2, lr, dense, packed):
+        """One launch of the site update on the resident sites: the entry point `packed` on nat2q, `dense` on nat2."""
+        self._sync_sites()
+        name, nat2 = (packed, self._nat2q) if self._packed else (dense, self._nat2)
+        _lib.check(getattr(self.dist_p.plan.lib, name)(ctypes.byref(data["struct"]), _ptr(g1), _ptr(g2), lr, _ptr(self._nat1), _ptr(nat2),
+                                                       _stream()), name)
+        self._sites_written()
+
+    def _step_graph(self, input_data, cache):
+        """`update_sites(input_data); classic_elbo(input_data)` captured once in a HIP graph (device route): returns a callable that
+        replays it and hands back the ELBO, a device scalar that every replay overwrites.  The site tensors and the sweep buffers keep
+        their addresses; a replay moves the sites behind the host's back, so it bumps their stamps and drops the cached results
+        (the marginals, the KL terms and the predict-lik pass kept in the attribute `cache`).  For the models whose step is
+        `_predict_lik(data, Y)` and a `_site_update` of two of its results: `_SITE_UPDATE` names them and the two entry points."""
+        data = self._data(input_data)
+        if data is None:
+            raise NotImplementedError("step_graph needs the device route: sorted, un-batched time points on the GPU")
+        # warm-up: every kernel of the step has run once (a site update at lr = 0 leaves the sites as they are), no state has moved
+        r = self._predict_lik(data, input_data[1])
+        self.classic_elbo(input_data)
+        g1, g2, dense, packed = self._SITE_UPDATE
+        self._site_update(data, r[g1], r[g2], 0.0, dense, packed)
+
+        def drop():
+            self._marg = self._kl_cache = None
+            setattr(self, cache, None)
+
+        drop()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self.update_sites(input_data)
+            e = self.classic_elbo(input_data)
+        drop()                                       # nothing ran during the capture
+
+        def step():
+            graph.replay()
+            wrote(self._nat1, self._nat2q if self._packed else self._nat2)
+            self._sites_written()
+            self.dist_p.plan.epoch += 1
+            drop()
+            return e
+        step.graph = graph
+        return step

@@ -7,7 +7,8 @@ spatial inducing point, D = Ms d_t).  It is SparseCVIGaussianProcess with a Kron
 
 and the conditional variance  c_i = k_s(x_i, x_i) - |a_i|^2 + |a_i|^2 H_t T^t_i H_t^T  (space_time_predict_f ->
 batch_base_conditional, :149-183; K_nn - Q_nn is not scaled by the time kernel's variance, as in the reference).  The marginals, the
-packed sites, the inverse / Cholesky form choice, the KL-terms cache and the one-launch ELBO are the parent's.
+packed sites, the inverse / Cholesky form choice, the KL-terms cache and the one-launch ELBO are SparseCVIGaussianProcess's; the data
+cache, the site-update dispatch, the pair marginals and the KL term of both devices are DenseRouteSparseCVI's.
 
 Routes: CPU tensors, unsorted times or VIDP_FUSED_SPARSE=0 take the torch route (searchsorted + index_add; w formed from a and h by
 broadcasting; conditional_statistics runs on the time kernel only, no [N, D, 2D] tensor); on the device with sorted times D <= 8
@@ -21,16 +22,16 @@ import os
 import torch
 
 from . import _lib
+from .conditionals import _cond_stats
 from .kernels import PiecewiseKernel, SparseSpatioTemporalKernel
 from .packed import _ptr, _stream
-from .sparse_pep import _cond_stats
-from .sparse_variational_cvi import SparseCVIGaussianProcess
-from .stamps import Stamp
+from .pair_sites import csr_offsets, initial_state
+from .sparse_variational_cvi import DenseRouteSparseCVI
 
 MAX_STATE_DIM = 32
 
 
-class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
+class SpatioTemporalSparseCVI(DenseRouteSparseCVI):
     """inducing_space [Ms, p], inducing_time [M_t] (sorted), kernel_space (vidp_amd.space_kernels), kernel_time (vidp_amd.kernels),
     likelihood (Gaussian, Bernoulli, Poisson, ScalarQuadratureLikelihood), mean_function: any callable X [N, p + 1] -> [N, 1].
     Data: X [N, p + 1] with time in the last column, Y [N, 1]."""
@@ -69,9 +70,6 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
     def inducing_space(self):
         return self._inducing_space
 
-    def _on_device(self):
-        return self.inducing_inputs.is_cuda
-
     # ---- per-data-set constants ----------------------------------------------------------------------------------------------------------
     def _features(self, X):
         """a [N, Ms], h [N, 2 d_t], c [N], interval index [N] of the points X [N, p + 1] (functions of the inputs and the kernels only)."""
@@ -106,19 +104,9 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
             raise ValueError("mean_function must return [N, 1]")
         return m.to(torch.float64)
 
-    def _data(self, input_data):
+    def _build_data(self, X):
         """Constants of the device routes (sorted times): CSR offsets, (a, h, c) or the materialised w, the mean function at the data;
         None where the torch route applies."""
-        X, _ = input_data
-        c = getattr(self, "_data_cache", None)
-        if c is not None and c[0].matches(X):
-            return c[1]
-        val = self._build_data(X)
-        self._data_cache = (Stamp(X), val)
-        return val
-
-    def _build_data(self, X):
-        """The constants of _data for the inputs X, uncached."""
         val = None
         z = self.inducing_inputs
         if (X.dim() == 2 and X.is_cuda and z.is_cuda and os.environ.get("VIDP_FUSED_SPARSE", "1") != "0"
@@ -130,10 +118,8 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
             else:
                 mk = lambda *s: torch.zeros(s, dtype=torch.float64, device=z.device)
                 a, h, cc, idx = mk(1, Ms), mk(1, 2 * d_t), mk(1), torch.zeros(0, dtype=torch.int64, device=z.device)
-            seg = torch.zeros(M + 2, dtype=torch.int32, device=z.device)
-            seg[1:] = torch.cumsum(torch.bincount(idx, minlength=M + 1), 0).to(torch.int32)
-            pm = self._kernel.initial_mean(()).to(z.device, torch.float64).contiguous()
-            pc = self._kernel.initial_covariance_matrix().to(z.device, torch.float64).contiguous()
+            seg = csr_offsets(idx, M + 1)
+            pm, pc = initial_state(self._kernel, z)
             factored = D > 8 and self._packed and os.environ.get("VIDP_ST_FACTORED", "1") != "0"
             if factored:
                 sd = _lib.StData()
@@ -200,76 +186,10 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
         fmu, fvar = self._predict_f_data(data)
         g1, g2 = self._gradients(fmu, fvar, Y, data["mean"])
         g1, g2 = g1.reshape(-1).contiguous(), g2.reshape(-1).contiguous()
-        lib, lr = self.dist_p.plan.lib, float(self.learning_rate)
-        self._sync_sites()
-        st = ctypes.byref(data["struct"])
-        if data["factored"]:
-            _lib.check(lib.mfgm_st_site_update_q(st, _ptr(g1), _ptr(g2), lr, _ptr(self._nat1), _ptr(self._nat2q), _stream()),
-                       "mfgm_st_site_update_q")
-            self._nat2 = None
-        elif self._packed:
-            _lib.check(lib.mfgm_sparse_site_update_q(st, _ptr(g1), _ptr(g2), lr, _ptr(self._nat1), _ptr(self._nat2q), _stream()),
-                       "mfgm_sparse_site_update_q")
-        else:
-            _lib.check(lib.mfgm_sparse_site_update(st, _ptr(g1), _ptr(g2), lr, _ptr(self._nat1), _ptr(self._nat2), _stream()),
-                       "mfgm_sparse_site_update")
-        self._sites_written()
+        self._site_update(data, g1, g2, float(self.learning_rate), "mfgm_sparse_site_update",
+                          "mfgm_st_site_update_q" if data["factored"] else "mfgm_sparse_site_update_q")
 
     # ---- torch route (the correctness anchor) ----------------------------------------------------------------------------------------------
-    def _dense_prior(self):
-        """CPU tensors (small models, the host tests): the prior precision over all inducing states as one dense matrix."""
-        c = getattr(self, "_dense_p", None)
-        if c is None:
-            z, d = self.inducing_inputs, self._kernel.state_dim
-            M = z.shape[0]
-            A, Q = self._kernel.transition_statistics_local(z[1:] - z[:-1])
-            Qi = torch.linalg.inv(Q)
-            P = torch.zeros((M * d, M * d), dtype=torch.float64)
-            P[:d, :d] = torch.linalg.inv(self._kernel.initial_covariance_matrix())
-            for t in range(M - 1):
-                lo, hi = slice(t * d, (t + 1) * d), slice((t + 1) * d, (t + 2) * d)
-                QA = Qi[t] @ A[t]
-                P[lo, lo] += A[t].T @ QA
-                P[hi, hi] += Qi[t]
-                P[hi, lo] -= QA
-                P[lo, hi] -= QA.T
-            c = self._dense_p = dict(P=P, logdet=torch.linalg.slogdet(P)[1])
-        return c
-
-    def _dense_posterior(self):
-        d, M = self._kernel.state_dim, self.inducing_inputs.shape[0]
-        b = torch.zeros((M + 2) * d, dtype=torch.float64)
-        Q = torch.zeros(((M + 2) * d, (M + 2) * d), dtype=torch.float64)
-        nat1, nat2 = self.nat1, self.nat2
-        for m in range(M + 1):
-            sl = slice(m * d, (m + 2) * d)
-            b[sl] += nat1[m]
-            Q[sl, sl] += -2.0 * nat2[m]
-        P = self._dense_prior()["P"] + Q[d:-d, d:-d]
-        S = torch.linalg.inv(P)
-        return P, S @ b[d:-d], S
-
-    def _pair_marginals(self):
-        """Means [M + 1, 2D] and covariances [M + 1, 2D, 2D] of the pairs of consecutive inducing states, the prior's initial state at
-        both ends (conditionals.py:424-470)."""
-        d, M = self._kernel.state_dim, self.inducing_inputs.shape[0]
-        if self._on_device():
-            m = self._marginals()
-            mu, Sig, Sub = m["mu"], m["Sig"], m["Sub"][:M - 1]
-        else:
-            _, mq, S = self._dense_posterior()
-            mu, blk, ar = mq.view(M, d), S.view(M, d, M, d), torch.arange(M)
-            Sig, Sub = blk[ar, :, ar, :], blk[ar[1:], :, ar[:-1], :]
-        dev = mu.device
-        pm = self._kernel.initial_mean(()).to(dev, torch.float64)[None]
-        pc = self._kernel.initial_covariance_matrix().to(dev, torch.float64)[None]
-        em, ec = torch.cat([pm, mu, pm], 0), torch.cat([pc, Sig, pc], 0)
-        zero = torch.zeros_like(pc)
-        es = torch.cat([zero, Sub, zero], 0)
-        top = torch.cat([ec[:-1], es.transpose(-1, -2)], -1)
-        bot = torch.cat([es, ec[1:]], -1)
-        return torch.cat([em[:-1], em[1:]], -1), torch.cat([top, bot], -2)
-
     def _predict_torch(self, X):
         """(fmu, fvar [N, 1] with the mean function, w [N, 2D], interval index) at any inputs, sorted or not."""
         a, h, c, idx = self._features(X)
@@ -286,18 +206,15 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
 
     def space_time_predict_f(self, inputs):
         """Marginal (mean, variance) [N, 1] of f at inputs [N, p + 1] (:149-183)."""
-        c = getattr(self, "_data_cache", None)
-        if c is not None and c[0].matches(inputs):
-            data = c[1]                                          # the training inputs: their constants and predictions are cached
-            if data is not None:
+        data = self._data((inputs,), keep=False)
+        if data is not None:                                         # sorted inputs on the device: the kernels of update_sites
+            kept = getattr(self, "_data_cache", None)
+            if kept is not None and data is kept[1]:                 # the training inputs: their predictions are cached too
                 return self._predict_f_data(data)
-        else:
-            data = self._build_data(inputs)
-            if data is not None:                                     # sorted inputs on the device: the kernels of update_sites
-                keep = getattr(self, "_pred_cache", None)
-                res = self._predict_compute(data)
-                self._pred_cache = keep
-                return res
+            keep = getattr(self, "_pred_cache", None)
+            res = self._predict_compute(data)
+            self._pred_cache = keep
+            return res
         fmu, fvar, _, _, _ = self._predict_torch(inputs)
         return fmu, fvar
 
@@ -310,18 +227,6 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
         lr = self.learning_rate
         self.nat1 = (1 - lr) * self.nat1 + lr * s1      # (the setters move the stamps)
         self.nat2 = (1 - lr) * self.nat2 + lr * s2
-
-    def _kl(self):
-        """KL[q(s(Z_t)) || p(s(Z_t))]."""
-        if not self._on_device():
-            pr = self._dense_prior()
-            P, mq, S = self._dense_posterior()
-            n = mq.shape[0]
-            return 0.5 * ((pr["P"] * S).sum() + mq @ pr["P"] @ mq - n - pr["logdet"] + torch.linalg.slogdet(P)[1])
-        m, pn, p = self._marginals(), self._prior_natural(), self.dist_p
-        s = m["packed"]
-        tr, mh = p.plan.kl_terms(s["Sig"], s["Sub"], s["x"], pn["nat"]["diag"], pn["nat"]["sub"], self._prior_mean_packed(), aD=-2.0, aS=-1.0)
-        return (0.5 * (tr + mh - float(p.T * p.d) + 2.0 * pn["nat"]["sumlogchol"] + 2.0 * m["logdetL"])).sum()
 
     def elbo_and_grad(self, input_data):
         raise NotImplementedError("elbo_and_grad is not implemented for SpatioTemporalSparseCVI: the spatial kernel and the Kronecker "
@@ -341,18 +246,3 @@ class SpatioTemporalSparseCVI(SparseCVIGaussianProcess):
         """log p(y* | data) per point: the likelihood's predict_log_density of space_time_predict_f (:238-246)."""
         X, Y = input_data
         return self._likelihood.predict_log_density(*self.space_time_predict_f(X), Y)
-
-    # ---- objects of the whole chain (device only) ------------------------------------------------------------------------------------------
-    def _need_device(self, what):
-        if not self._on_device():
-            raise NotImplementedError(f"{what} needs the model on the device; CPU tensors serve the torch route of small models only")
-
-    @property
-    def dist_p(self):
-        self._need_device("dist_p")
-        return SparseCVIGaussianProcess.dist_p.fget(self)
-
-    @property
-    def dist_q(self):
-        self._need_device("dist_q")
-        return SparseCVIGaussianProcess.dist_q.fget(self)
