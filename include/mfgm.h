@@ -622,6 +622,39 @@ int mfgm_sparse_cond_score(const mfgm_sparse_data* data, const mfgm_kernel_terms
                            const double* a, const double* b, const double* mu, const double* Sig, const double* Sub, double* score,
                            void* ws, int* info, void* stream);
 
+/* Mini-batch sparse CVI (csrc/mfgm_minibatch.h): the whole data pass of ONE batch of n time points t [n] IN ANY ORDER against the M
+ * inducing points z [M] (increasing), one lane per point, fp64, state dimension d = the terms' own <= 8.  Per point i:
+ *   interval   idx[i] = #{z_j < t_i} (searchsorted, side left: a point ON an inducing point belongs to the interval on its left); the gaps
+ *              t_i - z- and z+ - t_i, both ends padded at -/+ 1e10
+ *   row        w[i] = [w- | w+] [2d] and c[i] per term in covariance form, the formulas and the exact-Q rule of mfgm_sparse_cond_score:
+ *              Q_mp = Q2 + A2 Q1 A2^T,  x = Q_mp^-1 A2 Q1 h,  y = h - A2^T x,  w+ = x,  w- = A1^T y,  c = h^T Q1 y  (an exactly-zero Q_mp
+ *              block has x = 0; one that is neither positive definite nor zero sets *info)
+ *   marginal   fmu[i] = w . pmu_m + shift[i],  fvar[i] = c + w^T PC_m w  with the pair moments of interval m = idx[i] assembled from
+ *              mu [M, d], Sig [M, d, d], Sub [M, d, d] as mfgm_sparse_predict assembles them (prior_mean [d] / prior_cov [d, d] at m = 0 and
+ *              m = M, zero cross block there); shift [n] may be NULL: zero
+ *   likelihood kind 0: prediction only (y, ve, g1, g2, ve_sum must be NULL); MFGM_LIK_GAUSSIAN (param = variance; the formula of the readout
+ *              section), MFGM_LIK_BERNOULLI, MFGM_LIK_POISSON (mfgm_scalar_lik) at (fmu, fvar, y[i]):
+ *                ve[i] = scale VE,  g2[i] = scale dVE/dv,  g1[i] = scale (dVE/dmu - 2 dVE/dv (fmu - shift[i]))
+ *              -- the gradients with respect to the expectation parameters of the zero-mean part the sites live on.  A NaN y[i] is an
+ *              absent point: ve = g1 = g2 = 0 exactly, fmu / fvar still written.
+ * A non-finite t_i gives idx = 0, zero w and c, fmu = shift[i], fvar = 0 and zero ve, g1, g2; no lane reads outside an array whatever
+ * the data.  ve_sum [1] = sum_i ve[i] in a fixed order (lanes by a shuffle tree, wavefronts through ws in index order; no floating-
+ * point atomics: two calls give identical bits); ws: mfgm_sparse_batch_workspace_doubles(n) doubles, needed with ve_sum only.  Every
+ * output pointer may be NULL and is then not written.  No allocation, no host synchronisation (graph-capturable).  Returns 1, before
+ * any HIP call, for a null required argument, d > 8, M < 1, n < 0, an unknown kind, a parameter outside the ranges of mfgm_scalar_lik /
+ * mfgm_pep_sites, a scale that is not finite and positive, and whatever terms mfgm_packed_kernel_ssm rejects.  n = 0 returns 0, launches
+ * nothing and writes ve_sum = 0.
+ * mfgm_sparse_batch_seg: the CSR offsets seg [M + 2] of a batch SORTED in time (NaN last): seg[0] = 0, seg[m + 1] = #{t_i <= z_m},
+ * seg[M + 1] = n -- the intervals of idx above; one lane per inducing point and one binary search each (no histogram, no atomics, no
+ * scan; graph-capturable).  With w of the sorted batch, what mfgm_sparse_site_update takes as seg and w. */
+size_t mfgm_sparse_batch_workspace_doubles(long n);
+int mfgm_sparse_batch_predict_lik(const mfgm_kernel_terms* terms, int M, const double* z, long n, const double* t, const double* shift,
+                                  int kind, double param, double scale, const double* y, const double* prior_mean,
+                                  const double* prior_cov, const double* mu, const double* Sig, const double* Sub, int* idx, double* w,
+                                  double* c, double* fmu, double* fvar, double* ve, double* g1, double* g2, double* ve_sum, void* ws,
+                                  int* info, void* stream);
+int mfgm_sparse_batch_seg(int M, const double* z, long n, const double* t_sorted, int* seg, void* stream);
+
 /* A piecewise-stationary kernel (kernels/piecewise_stationary.py `PiecewiseKernel`): nregion - 1 change points c_k cut the time axis
  * into nregion regions, region r(t) = #{c_k <= t} (a point on a change point belongs to the region after it).  All regions share
  * base's structure (nterm, nfactor, offset, kind) and jitter; region r has the rates rate[r], variances var[r] (both indexed as

@@ -26,4 +26,7 @@ def __getattr__(name):
     if name == "FactorAnalysisSparseCVI":
         from .factor_analysis_variational import FactorAnalysisSparseCVI
         return FactorAnalysisSparseCVI
+    if name == "MiniBatchSitesTrainer":
+        from .trainers import MiniBatchSitesTrainer
+        return MiniBatchSitesTrainer
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

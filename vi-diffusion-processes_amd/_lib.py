@@ -66,6 +66,11 @@ EXPORTS = {
     "mfgm_packed_kernel_score": (ctypes.c_int, [ctypes.c_void_p] * 10),
     "mfgm_sparse_cond_score_workspace_doubles": (ctypes.c_size_t, [ctypes.c_int]),
     "mfgm_sparse_cond_score": (ctypes.c_int, [ctypes.c_void_p] * 13),
+    "mfgm_sparse_batch_workspace_doubles": (ctypes.c_size_t, [ctypes.c_long]),
+    "mfgm_sparse_batch_predict_lik": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double]
+                                      + [ctypes.c_void_p] * 18),
+    "mfgm_sparse_batch_seg": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mfgm_packed_piecewise_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_packed_leg_ssm": (ctypes.c_int, [ctypes.c_void_p] * 8),
     "mfgm_leg_transitions": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long] + [ctypes.c_void_p] * 4),

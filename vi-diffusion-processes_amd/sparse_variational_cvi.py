@@ -14,12 +14,16 @@ import torch
 from . import _lib
 from ._lib import FULL, SYM, VEC
 from .conditionals import _conditional_statistics, conditional_statistics
+from .likelihoods import Bernoulli, Gaussian, Poisson
 from .packed import Plan, _ptr, _stream
 from .pair_sites import chain_kl, csr_offsets, dense_kl, initial_state, need_device, on_device, pair_marginals
 from .posterior import ConditionalProcess
 from .ssm_gaussian_transformations import naturals_to_ssm_params_packed
 from .stamps import Stamp, wrote
 from .variational_cvi import back_project_nats
+
+# the likelihoods of the native mini-batch pass (mfgm_sparse_batch_predict_lik): exactly these classes
+_BATCH_KINDS = {Gaussian: _lib.LIK_GAUSSIAN, Bernoulli: _lib.LIK_BERNOULLI, Poisson: _lib.LIK_POISSON}
 
 
 class SparseCVIGaussianProcess:
@@ -30,11 +34,23 @@ class SparseCVIGaussianProcess:
     takes interval M) and the data points inside them.  Per step three small collectives cross processes: the site on the right edge
     (one [2d + 4d^2] block per neighbour pair, all-gathered after `update_sites`), the exchange level of the factorisation
     (n_X (3d^2 + 2d) doubles) and the four scalars of the ELBO.  Every process is handed the same (time_points, observations) and keeps
-    its own slice; the arrays over inducing states keep global indices and are valid on the owned range.  State dimension > 8 only."""
+    its own slice; the arrays over inducing states keep global indices and are valid on the owned range.  State dimension > 8 only.
 
-    def __init__(self, kernel, inducing_points, likelihood, mean_function=None, learning_rate=0.1, shard=None):
+    `num_data=N_total` puts the model in MINI-BATCH mode: `update_sites` and `classic_elbo` then take a batch
+    (t [n], y [n, 1]) drawn from a data set of N_total points, in any order and a new tensor every step, and weigh its terms by
+    num_data / n -- the reference's sparse variational models (models/sparse_variational.py:184-192).  Not with `shard=`."""
+
+    num_data = None          # (a class attribute: the models built on this class do not take the keyword)
+
+    def __init__(self, kernel, inducing_points, likelihood, mean_function=None, learning_rate=0.1, shard=None, num_data=None):
         self._kernel, self._likelihood = kernel, likelihood
         self.learning_rate = learning_rate
+        if num_data is not None:
+            if shard is not None:
+                raise NotImplementedError("mini-batches (num_data=) of a chain shared between processes (shard=) are not implemented")
+            if not float(num_data) > 0.0:
+                raise ValueError(f"num_data must be positive, got {num_data!r}")
+            self.num_data = float(num_data)
         self.inducing_inputs = inducing_points
         M, sd = inducing_points.shape[-1], kernel.state_dim
         dev, dt = inducing_points.device, torch.float64
@@ -390,27 +406,44 @@ class SparseCVIGaussianProcess:
         return res
 
     def update_sites(self, input_data):
-        """theta_m <- (1 - rho) theta_m + rho g_m, g_m = data gradients projected through p(f_k | v_m) (sparse_variational_cvi.py:176-221)."""
+        """theta_m <- (1 - rho) theta_m + rho g_m, g_m = data gradients projected through p(f_k | v_m) (sparse_variational_cvi.py:176-221).
+        In mini-batch mode (num_data=) input_data is one batch of n points in any order and g_m is the batch's sum times num_data / n.
+        Unlike the reference, whose sparse variational models scale the bound only, the scale enters the site gradient too: without
+        it the fixed point of the updates is the posterior of n observations, not of num_data.  A site whose interval holds no batch
+        point decays."""
+        if self.num_data is not None:
+            return self._update_sites_batch(input_data)
         data = self._data(input_data)
         if data is None:
             return self._update_sites_generic(input_data)
-        time_points, observations = input_data
+        # the SAME tensor object for the owned observations every step, so that a likelihood's per-observation-tensor caches hit (a
+        # fresh slice object never would)
+        self._update_sites_data(data, self._own_observations(data, input_data[1]))
+
+    def _update_sites_data(self, data, y_own, scale=None):
+        """update_sites on the constants `data` of a sorted data set with the observations of its owned points; scale: the weight of
+        every point's gradient (a mini-batch), None for 1."""
         fx_mus, fx_covs = self._predict_f_data(data)
         # the gradients alone: the reference's local_objective_and_gradients also returns the objective value, which update_sites drops
-        # (:187-189) -- eight element-wise launches over the observations per step here; and the SAME tensor object for the owned
-        # observations every step, so that a likelihood's per-observation-tensor caches hit (a fresh slice object never would)
-        grads = self._likelihood.ve_gradients_expectation(fx_mus, fx_covs, self._own_observations(data, observations))
+        # (:187-189) -- eight element-wise launches over the observations per step here
+        grads = self._likelihood.ve_gradients_expectation(fx_mus, fx_covs, y_own)
         g1, g2 = grads[0].reshape(-1).contiguous(), grads[1].reshape(-1).contiguous()
         if self._time_mean is not None:
             # from the expectation parameters of f to those of g = f - m, which the sites are on: d/dmu - 2 d/dvar mu_g
             g1 = g1 + 2.0 * g2 * self._mean_at(data).reshape(-1)
+        if scale is not None:
+            g1, g2 = scale * g1, scale * g2
+        self._site_update_launch(data["struct"], g1, g2)
+
+    def _site_update_launch(self, struct, g1, g2):
+        """sites <- (1 - rho) sites + rho sum_{i in interval} (g1_i w_i, g2_i w_i w_i^T) on the resident sites, in place."""
         pl = self.dist_p.plan
         self._sync_sites()
         if self._packed:
-            _lib.check(pl.lib.mfgm_sparse_site_update_q(ctypes.byref(data["struct"]), _ptr(g1), _ptr(g2), float(self.learning_rate),
+            _lib.check(pl.lib.mfgm_sparse_site_update_q(ctypes.byref(struct), _ptr(g1), _ptr(g2), float(self.learning_rate),
                                                         _ptr(self._nat1), _ptr(self._nat2q), _stream()), "mfgm_sparse_site_update_q")
         else:
-            _lib.check(pl.lib.mfgm_sparse_site_update(ctypes.byref(data["struct"]), _ptr(g1), _ptr(g2), float(self.learning_rate),
+            _lib.check(pl.lib.mfgm_sparse_site_update(ctypes.byref(struct), _ptr(g1), _ptr(g2), float(self.learning_rate),
                                                       _ptr(self._nat1), _ptr(self._nat2), _stream()), "mfgm_sparse_site_update")
         self._sites_written()
         if self._shard is not None:
@@ -440,12 +473,14 @@ class SparseCVIGaussianProcess:
             t.copy_(sh.allreduce(own))
         self._sites_written()
 
-    def _update_sites_generic(self, input_data):
+    def _update_sites_generic(self, input_data, scale=None):
         time_points, observations = input_data
         fx_mus, fx_covs = self.posterior.predict_f(time_points)
         _, grads = self.local_objective_and_gradients(fx_mus, fx_covs, observations)
         if self._time_mean is not None:
             grads = (grads[0] + 2.0 * grads[1] * self._time_mean(time_points), grads[1])      # (as in update_sites)
+        if scale is not None:
+            grads = (scale * grads[0], scale * grads[1])                                       # (a mini-batch)
         H = self._kernel.generate_emission_model(time_points).emission_matrix
         P, _ = conditional_statistics(time_points, self.inducing_inputs, self._kernel)
         theta_linear, lik_nat2 = back_project_nats(grads[0], grads[1], H @ P)
@@ -458,15 +493,26 @@ class SparseCVIGaussianProcess:
 
     def classic_elbo(self, input_data):
         """sum_i E_q log p(y_i | f_i) - KL[q(s_Z) || p(s_Z)] (sparse_variational_cvi.py:270-292)."""
-        time_points, observations = input_data
+        if self.num_data is not None:
+            return self._classic_elbo_batch(input_data)
         data = self._data(input_data)
         if data is None:
-            q = self.dist_q
-            fx_mus, fx_covs = ConditionalProcess(q, self._kernel, self.inducing_inputs, self._time_mean).predict_f(time_points)
-            ve = self._likelihood.variational_expectations(fx_mus, fx_covs, observations).sum()
-            return ve - q.kl_divergence(self.dist_p).sum()
+            return self._classic_elbo_generic(input_data)
+        return self._classic_elbo_data(data, self._own_observations(data, input_data[1]))
+
+    def _classic_elbo_generic(self, input_data, scale=1.0):
+        time_points, observations = input_data
+        q = self.dist_q
+        fx_mus, fx_covs = ConditionalProcess(q, self._kernel, self.inducing_inputs, self._time_mean).predict_f(time_points)
+        ve = self._likelihood.variational_expectations(fx_mus, fx_covs, observations).sum()
+        if scale != 1.0:
+            ve = scale * ve
+        return ve - q.kl_divergence(self.dist_p).sum()
+
+    def _classic_elbo_data(self, data, y_own, scale=1.0):
+        """classic_elbo on the constants `data` of a sorted data set with the observations of its owned points; scale: the weight of
+        the expectation term (a mini-batch)."""
         fx_mus, fx_covs = self._predict_f_data(data)
-        y_own = self._own_observations(data, observations)
         ve_terms = getattr(self._likelihood, "variational_expectations_terms", None)
         kc = getattr(self, "_kl_cache", None)
         if ve_terms is not None and self._shard is None and kc is not None and self._current(kc[0]):
@@ -474,6 +520,8 @@ class SparseCVIGaussianProcess:
             # NaN-poisoned when a pivot block of the factorisation was not positive definite
             m, pn, p = self._marginals(), self._prior_natural(), self.dist_p
             c, w, (t1, t2) = ve_terms(fx_mus, fx_covs, y_own)
+            if scale != 1.0:
+                c, w = scale * c, scale * w
             terms = torch.cat([t1, t2, kc[1].reshape(1), kc[2].reshape(1), pn["nat"]["sumlogchol"].reshape(1), m["logdetL"].reshape(1)])
             wts = (ctypes.c_double * 6)(w, w, -0.5, -0.5, -1.0, -1.0)
             out = torch.empty(1, dtype=torch.float64, device=terms.device)
@@ -482,6 +530,8 @@ class SparseCVIGaussianProcess:
             return out[0]
         ve_sum = getattr(self._likelihood, "variational_expectations_sum", None)
         ve = ve_sum(fx_mus, fx_covs, y_own) if ve_sum is not None else self._likelihood.variational_expectations(fx_mus, fx_covs, y_own).sum()
+        if scale != 1.0:
+            ve = scale * ve
         # KL[q || p] from the marginal blocks of q and the prior's naturals (state_space_model.py:528-593); the prior mean is zero
         m, pn = self._marginals(), self._prior_natural()
         p = self.dist_p
@@ -512,6 +562,104 @@ class SparseCVIGaussianProcess:
     def loss(self, input_data):
         return -self.classic_elbo(input_data)
 
+    # ---- mini-batch mode (num_data=; csrc/mfgm_minibatch.h) -----------------------------------------------------------
+    # For a batch (t [n], y [n, 1]) of a data set of num_data points, with scale = num_data / n:
+    #   update_sites:  theta_m <- (1 - rho) theta_m + rho scale sum_{i in batch and m} (g1_i w_i, g2_i w_i w_i^T); a site whose interval
+    #                  holds no batch point decays.  The scale enters the site gradient too: the reference's sparse variational models
+    #                  scale the bound only, and without it the fixed point of the site updates is the posterior of n observations,
+    #                  not of num_data.
+    #   classic_elbo:  scale sum_i E_q log p(y_i | f_i) - KL[q(s_Z) || p(s_Z)].
+    # The batch is sorted in time (plumbing: torch.sort and a gather of y); nothing of it is kept beyond the step, and the constants of
+    # a full data set in _data_cache stay where they are.  The native route (_batch_native) makes the whole data pass in one launch
+    # from the time points alone and never looks at the data on the host; the torch route is _build_data's formulas, uncached.
+    def _batch_native(self, time_points):
+        from .kernels import IndependentMultiOutput, PiecewiseKernel, StationaryKernel
+        k = self._kernel
+        if (os.environ.get("VIDP_NATIVE_MINIBATCH", "1") == "0" or not time_points.is_cuda or time_points.dim() != 1
+                or self.inducing_inputs.dim() != 1 or k.state_dim > 8 or type(self._likelihood) not in _BATCH_KINDS
+                or not isinstance(k, StationaryKernel) or isinstance(k, (PiecewiseKernel, IndependentMultiOutput))):
+            return False
+        terms = k._terms()
+        return terms is not None and len(terms) <= 8
+
+    def _batch_sorted(self, input_data):
+        """(t sorted, y in that order [n, 1], num_data / n) of a batch."""
+        t, y = input_data
+        if t.dim() != 1 or t.shape[0] == 0:
+            raise ValueError("a mini-batch is (time_points [n], observations [n, 1]) with n >= 1")
+        n = int(t.shape[0])
+        ts, perm = torch.sort(t, stable=True)
+        return ts.contiguous(), y.reshape(n, -1)[perm].contiguous(), self.num_data / n
+
+    def _batch_pass(self, input_data):
+        """The native data pass of a batch: dict(struct: the SparseData of the sorted batch for the site update, g1, g2, ve [n] already
+        scaled, ve_sum [1], fmu, fvar [n]); kept for the same batch object while the sites do not move (the Stamp rules)."""
+        t, y = input_data
+        c = getattr(self, "_batch_cache", None)
+        if c is not None and c["native"] and c["stamp"].matches(t, y) and self._current(c["key"]):
+            return c
+        ts, ys, scale = self._batch_sorted(input_data)
+        k = getattr(self, "_batch_consts", None)
+        if k is None:
+            z = self.inducing_inputs.contiguous()
+            k = self._batch_consts = dict(z=z, terms=self._kernel._terms_struct(), init=initial_state(self._kernel, z))
+        z, (pm, pc) = k["z"], k["init"]
+        M, d, n, dev = int(z.shape[0]), self._kernel.state_dim, int(ts.shape[0]), ts.device
+        shift = None if self._time_mean is None else self._time_mean(ts).reshape(-1).contiguous()
+        m = self._marginals()
+        pl = self.dist_p.plan
+        lik = self._likelihood
+        kind = _BATCH_KINDS[type(lik)]
+        param = lik.variance if kind == _lib.LIK_GAUSSIAN else lik.param
+        out = torch.empty((6, n), dtype=torch.float64, device=dev)          # c, fmu, fvar, ve, g1, g2
+        w = torch.empty((n, 2 * d), dtype=torch.float64, device=dev)
+        ve_sum = torch.empty(1, dtype=torch.float64, device=dev)
+        ws = torch.empty(int(pl.lib.mfgm_sparse_batch_workspace_doubles(n)), dtype=torch.float64, device=dev)
+        seg = torch.empty(M + 2, dtype=torch.int32, device=dev)
+        _lib.check(pl.lib.mfgm_sparse_batch_predict_lik(ctypes.byref(k["terms"]), M, _ptr(z), n, _ptr(ts), _ptr(shift), kind, float(param),
+                                                        float(scale), _ptr(ys), _ptr(pm), _ptr(pc), _ptr(m["mu"]), _ptr(m["Sig"]),
+                                                        _ptr(m["Sub"]), None, _ptr(w), *(_ptr(o) for o in out), _ptr(ve_sum), _ptr(ws),
+                                                        _ptr(pl.info), _stream()), "mfgm_sparse_batch_predict_lik")
+        _lib.check(pl.lib.mfgm_sparse_batch_seg(M, _ptr(z), n, _ptr(ts), _ptr(seg), _stream()), "mfgm_sparse_batch_seg")
+        sd = _lib.SparseData()
+        sd.M, sd.d, sd.N, sd.m_lo, sd.m_hi = M, d, n, 0, M + 1
+        sd.seg, sd.w, sd.c, sd.prior_mean, sd.prior_cov = seg.data_ptr(), w.data_ptr(), out[0].data_ptr(), pm.data_ptr(), pc.data_ptr()
+        c = dict(native=True, stamp=Stamp(t, y), key=self._key(), struct=sd, keep=(seg, w, out, ts, ys, shift), fmu=out[1], fvar=out[2],
+                 ve=out[3], g1=out[4], g2=out[5], ve_sum=ve_sum, scale=scale)
+        self._batch_cache = c
+        return c
+
+    def _batch_torch(self, input_data):
+        """The torch route's view of a batch: dict(data: _build_data of the sorted time points or None, ts, ys, scale); kept for the
+        same batch object (the constants depend on the time points and the kernel only)."""
+        t, y = input_data
+        c = getattr(self, "_batch_cache", None)
+        if c is not None and not c["native"] and c["stamp"].matches(t, y):
+            return c
+        ts, ys, scale = self._batch_sorted(input_data)
+        c = dict(native=False, stamp=Stamp(t, y), data=self._build_data(ts), ts=ts, ys=ys, scale=scale)
+        self._batch_cache = c
+        return c
+
+    def _update_sites_batch(self, input_data):
+        if self._batch_native(input_data[0]):
+            c = self._batch_pass(input_data)
+            return self._site_update_launch(c["struct"], c["g1"], c["g2"])
+        c = self._batch_torch(input_data)
+        if c["data"] is None:
+            return self._update_sites_generic((c["ts"], c["ys"]), scale=c["scale"])
+        self._update_sites_data(c["data"], c["ys"], scale=c["scale"])
+
+    def _classic_elbo_batch(self, input_data):
+        if self._batch_native(input_data[0]):
+            c = self._batch_pass(input_data)
+            kl = chain_kl(self.dist_p, self._marginals(), self._prior_natural(), self._prior_mean_packed()).sum()
+            return c["ve_sum"][0] - kl
+        c = self._batch_torch(input_data)
+        if c["data"] is None:
+            return self._classic_elbo_generic((c["ts"], c["ys"]), scale=c["scale"])
+        return self._classic_elbo_data(c["data"], c["ys"], scale=c["scale"])
+
     # ---- kernel hyper-parameters (DESIGN.md section 21) ------------------------------------------------------------------------------------
     def elbo_and_grad(self, input_data):
         """(classic_elbo(input_data), its exact gradient with respect to the kernel's hyper-parameters with the sites held fixed): the
@@ -519,6 +667,8 @@ class SparseCVIGaussianProcess:
         models.  What the reference's sparse notebooks get from a GradientTape over `model.loss` between two site steps.  One chain,
         every process its own: `shard=` is not covered."""
         from . import hyper
+        if self.num_data is not None:
+            raise NotImplementedError("elbo_and_grad on mini-batches (num_data=) is not implemented")
         if self._time_mean is not None:
             raise NotImplementedError("elbo_and_grad with a mean function is not implemented")
         hyper.precheck(self._kernel)
@@ -536,6 +686,7 @@ class SparseCVIGaussianProcess:
         self._pn, self._pmu = None, None
         self._data_cache = None
         self._marg, self._pred_cache, self._kl_cache = None, None, None
+        self._batch_consts, self._batch_cache = None, None
         self.__dict__.pop("_theta_bufs", None)
         self.__dict__.pop("_sweep_bufs", None)
         if hasattr(self._time_mean, "kernel_changed"):

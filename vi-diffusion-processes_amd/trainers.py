@@ -556,3 +556,61 @@ class KernelHyperTrainer:
                     self.model.update_sites()
             losses.append(self.step())
         return losses
+
+
+class MiniBatchSitesTrainer:
+    """Stochastic CVI for a SparseCVIGaussianProcess in mini-batch mode (`num_data=`): epochs of
+    without-replacement batches of `batch_size` points of input_data = (time_points [N], observations [N, 1]), one `update_sites` per
+    batch at the decaying learning rate  rho_k = lr0 / (1 + (k - 1) decay),  k = 1, 2, ...  (decay = 1: the Robbins-Monro 1 / k under
+    which one epoch of a Gaussian model is the full-batch step).  The batches come from a seeded torch.Generator on the data's device,
+    one randperm per epoch and no host synchronisation per step; the same seed gives the same batches.  The last batch of an epoch is
+    the smaller remainder when batch_size does not divide N, and is weighed by its own size."""
+
+    def __init__(self, model, input_data, batch_size, seed, lr0=1.0, decay=1.0):
+        if getattr(model, "num_data", None) is None:
+            raise ValueError("MiniBatchSitesTrainer needs a model in mini-batch mode: SparseCVIGaussianProcess(..., num_data=N)")
+        t, y = input_data
+        if t.dim() != 1 or int(t.shape[0]) < 1:
+            raise ValueError("input_data is (time_points [N], observations [N, 1]) with N >= 1")
+        if not 1 <= int(batch_size):
+            raise ValueError(f"batch_size must be at least 1, got {batch_size!r}")
+        self.model = model
+        self.input_data = (t, y.reshape(int(t.shape[0]), -1))
+        self.batch_size = min(int(batch_size), int(t.shape[0]))
+        self.lr0, self.decay = float(lr0), float(decay)
+        self._gen = torch.Generator(device=t.device)
+        self._gen.manual_seed(int(seed))
+        self._perm, self._at = None, 0
+        self.k = 0               # steps taken
+        self.last_batch = None
+
+    def learning_rate(self, k):
+        return self.lr0 / (1.0 + (k - 1) * self.decay)
+
+    def next_batch(self):
+        """The next batch of the current epoch (a new epoch draws a new permutation)."""
+        t, y = self.input_data
+        N = int(t.shape[0])
+        if self._perm is None or self._at >= N:
+            self._perm, self._at = torch.randperm(N, generator=self._gen, device=t.device), 0
+        sel = self._perm[self._at:self._at + self.batch_size]
+        self._at += self.batch_size
+        return t[sel], y[sel]
+
+    def step(self):
+        """One site update on the next batch at the step's learning rate."""
+        self.k += 1
+        self.model.learning_rate = self.learning_rate(self.k)
+        self.last_batch = self.next_batch()
+        self.model.update_sites(self.last_batch)
+
+    def fit(self, n_steps):
+        for _ in range(int(n_steps)):
+            self.step()
+        return self
+
+    def elbo_estimate(self):
+        """The scaled bound on the last batch at the current sites (a device scalar)."""
+        if self.last_batch is None:
+            raise ValueError("no step has been taken")
+        return self.model.classic_elbo(self.last_batch)
