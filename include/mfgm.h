@@ -1211,6 +1211,25 @@ int mfgm_panel_predict_lik(const mfgm_plan* plan, const mfgm_panel_data* data, i
  * mfgm_pep_sites), lr outside [0, 1], or a missing pointer when there is a point to cover. */
 int mfgm_panel_site_update(const mfgm_panel_data* data, const double* g1, const double* g2, double lr, double* nat1, double* nat2,
                            void* stream);
+/* Score of the panel's sparse-CVI bound with respect to the kernel terms' parameters THROUGH THE CONDITIONALS of the B N data points,
+ * at fixed posteriors of the B series and summed over them (csrc/mfgm_panel_score.h):
+ *   sum_{b,i} a_bi d fmu_bi + b_bi d fvar_bi,   fmu = w . mu_pair,   fvar = c + w^T Sigma_pair w,
+ * the quantity, the covariance form and the reverse mode of mfgm_sparse_cond_score, one lane per (series, point), with the pair
+ * (state m - 1, state m) of series b, m = idx[b, i] (clamped to 0 .. M), read from the packed x (VEC), Sig (SYM), Sub (FULL) of the
+ * plan as mfgm_panel_predict_lik takes them; the prior (prior_mean, prior_cov of `data`) pads the intervals 0 and M, which add
+ * b w^T dPinf w.  gap_lo, gap_hi [B, N]: t - z- and z+ - t, the two ends padded by the caller (conditionals.py, interval_gaps);
+ * a, b [B, N]: d ve / d fmu and d ve / d fvar, both 0 for an absent point, which then adds exactly 0.0 to every slot (its time is
+ * finite).  data: idx, w, prior_mean, prior_cov are read, seg and c are not.  score: natural [8, 3, 2] in the layout of
+ * mfgm_packed_kernel_score (the CALLER's factor order), absent slots exact zeros.  *info is set when a Q_mp block is neither positive
+ * definite nor exactly zero.  ws: mfgm_panel_cond_score_workspace_doubles(B, N) doubles (one partial per wavefront of 64 points and
+ * plane, summed in index order: no floating-point atomics, two calls give identical bits; one series alone gives the bits of
+ * mfgm_sparse_cond_score).  B N = 0 writes a zero score.  Returns 1, before any HIP call, for a null plan, data, terms or score, any
+ * other null argument while B N > 0 (Sub may be NULL when M = 1), d outside 1 .. 8, a wide plan, a plan whose B, T, d differ from
+ * data's B, M, d, and whatever terms mfgm_packed_kernel_ssm rejects. */
+size_t mfgm_panel_cond_score_workspace_doubles(int B, int N);
+int mfgm_panel_cond_score(const mfgm_plan* plan, const mfgm_panel_data* data, const mfgm_kernel_terms* terms, const double* gap_lo,
+                          const double* gap_hi, const double* a, const double* b, const double* x, const double* Sig, const double* Sub,
+                          double* score, void* ws, int* info, void* stream);
 
 /* ---- factor-analysis sparse CVI (factor_analysis_variational.py; markovflow/kernels/sde_kernel.py:881; csrc/mfgm_fa.h) ------------------
  * Sparse CVI on pairs of inducing states whose state stacks L independent latent processes g_l (the layout of mfgm_ml_data), observed

@@ -184,6 +184,8 @@ EXPORTS = {
     "mfgm_panel_theta": (ctypes.c_int, [ctypes.c_void_p] * 10),
     "mfgm_panel_predict_lik": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 11),
     "mfgm_panel_site_update": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
+    "mfgm_panel_cond_score_workspace_doubles": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "mfgm_panel_cond_score": (ctypes.c_int, [ctypes.c_void_p] * 14),
     "mfgm_fa_predict_lik": (ctypes.c_int, [ctypes.c_void_p] * 16),
     "mfgm_fa_site_update": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),
     "mfgm_fa_site_update_q": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 3),

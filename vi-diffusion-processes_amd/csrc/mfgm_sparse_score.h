@@ -149,9 +149,10 @@ MFGM_DEV void pair_cotangent(const CondScoreArgs& A, int m, bool hi, int O, cons
     }
 }
 
-// One term of shape (D0, D1, D2) for the lane's data point.
-template <int NMAX, int D0, int D1, int D2>
-MFGM_DEV void cond_score_term(const CondScoreArgs& A, const TermDesc& td0, int m, const double* __restrict__ w, double d1, double d2,
+// One term of shape (D0, D1, D2) for the lane's data point.  ARGS: CondScoreArgs, or another struct with sp.M, sp.d, jitter and a
+// pair_cotangent of its own (the panel's reads the packed moments of a B-chain plan, mfgm_panel_score.h).
+template <int NMAX, int D0, int D1, int D2, class ARGS>
+MFGM_DEV void cond_score_term(const ARGS& A, const TermDesc& td0, int m, const double* __restrict__ w, double d1, double d2,
                               double av, double bv, double (&acc)[6], int& bad) {
     constexpr int N = D0 * D1 * D2, NT = MFGM_NTRI(N);
     if constexpr (N <= NMAX) {
@@ -298,22 +299,11 @@ MFGM_DEV void cond_score_term(const CondScoreArgs& A, const TermDesc& td0, int m
     }
 }
 
-template <int NMAX>
-static __global__ __launch_bounds__(64) void k_sparse_cond_score(CondScoreArgs A, KernelTermsDev kt) {
-    const int gi = blockIdx.x * 64 + threadIdx.x;
-    const int N = A.sp.N;
-    const bool active = gi < N;
-    const int i = active ? gi : N - 1;      // idle lanes of the last wavefront repeat its last point and add nothing
-    // the interval of the point: the last m with seg[m] <= i
-    int lo = 0, hi = A.sp.M;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (A.sp.seg[mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    const int m = lo;
-    const double* w = A.sp.w + (size_t)i * (2 * A.sp.d);
-    const double d1 = A.gap_lo[i], d2 = A.gap_hi[i], av = A.a[i], bv = A.b[i];
+// The lane's point through every term: the uniform loop over the terms, each term's six sums added over the wavefront by a fixed
+// shuffle tree into part[plane][blockIdx.x] (an idle lane, active == false, adds nothing).  Returns the lane's bad-block flag.
+template <int NMAX, class ARGS>
+MFGM_DEV int cond_score_lane(const ARGS& A, const KernelTermsDev& kt, int m, const double* __restrict__ w, double d1, double d2, double av,
+                             double bv, bool active, double* __restrict__ part, int nblk) {
     int bad = 0;
     for (int c = 0; c < kt.nterm; ++c) {
         TermDesc td;
@@ -341,9 +331,28 @@ static __global__ __launch_bounds__(64) void k_sparse_cond_score(CondScoreArgs A
             double s = active ? acc[k] : 0.0;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-            if (threadIdx.x == 0) A.part[(size_t)(c * 6 + k) * A.nblk + blockIdx.x] = s;
+            if (threadIdx.x == 0) part[(size_t)(c * 6 + k) * nblk + blockIdx.x] = s;
         }
     }
+    return bad;
+}
+
+template <int NMAX>
+static __global__ __launch_bounds__(64) void k_sparse_cond_score(CondScoreArgs A, KernelTermsDev kt) {
+    const int gi = blockIdx.x * 64 + threadIdx.x;
+    const int N = A.sp.N;
+    const bool active = gi < N;
+    const int i = active ? gi : N - 1;      // idle lanes of the last wavefront repeat its last point and add nothing
+    // the interval of the point: the last m with seg[m] <= i
+    int lo = 0, hi = A.sp.M;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (A.sp.seg[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    const int m = lo;
+    const double* w = A.sp.w + (size_t)i * (2 * A.sp.d);
+    const int bad = cond_score_lane<NMAX>(A, kt, m, w, A.gap_lo[i], A.gap_hi[i], A.a[i], A.b[i], active, A.part, A.nblk);
     // as in k_kernel_ssm: every writer of this word in the launch writes 1
     if (bad && *A.info == 0) *A.info = 1;
 }

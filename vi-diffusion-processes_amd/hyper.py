@@ -25,7 +25,9 @@ VIDP_NATIVE_SCORE=0 forces the fallback.
 The sparse CVI model (SparseCVIGaussianProcess.elbo_and_grad) differentiates its ELBO at fixed sites with the
 same two routes for the chain part, fed with the moments displaced by a Fisher-vector product, plus a part through the conditionals
 of the data points: one launch of mfgm_sparse_cond_score (csrc/mfgm_sparse_score.h) natively, autograd through `_parts` otherwise
-(`sparse_elbo_grad`; VIDP_NATIVE_SPARSE_SCORE=0 forces the torch route).
+(`sparse_elbo_grad`; VIDP_NATIVE_SPARSE_SCORE=0 forces the torch route).  PanelSparseCVI.elbo_and_grad is the
+same decomposition with a leading series axis, summed over the series: one batched Fisher-vector product, one batched chain score and
+one launch of mfgm_panel_cond_score (csrc/mfgm_panel_score.h) on the packed marginals of the B-chain plan (`panel_elbo_grad`).
 """
 import math
 import os
@@ -90,6 +92,17 @@ def _check_terms(kernel, terms):
             raise ValueError(_NO_SCORE)
 
 
+def _leaves_from_score(kernel, g):
+    """The chain rule from a score g [8, 3, 2] (CPU) with respect to every factor's (rate, var) to the kernel's leaves: one scalar
+    autograd call on the host."""
+    leaves = kernel.hyperparameter_leaves("cpu")
+    objective = torch.zeros((), dtype=torch.float64)
+    for c, factors in enumerate(kernel._terms_t(leaves)):
+        for f, (_, rate, var) in enumerate(factors):
+            objective = objective + rate * g[c, f, 0] + var * g[c, f, 1]
+    return _grads_of(leaves, objective)
+
+
 def score_native(kernel, plan, time_deltas, moments):
     """Kernel gradients (structure of hyperparameter_leaves(), CPU) from the packed centred moments, summed over the chains."""
     from .kernels import _NOT_PD
@@ -100,13 +113,7 @@ def score_native(kernel, plan, time_deltas, moments):
         plan.check_info()
     except ArithmeticError as e:
         raise ArithmeticError(_NOT_PD) from e
-    g = g.sum(0).cpu()
-    leaves = kernel.hyperparameter_leaves("cpu")
-    objective = torch.zeros((), dtype=torch.float64)
-    for c, factors in enumerate(kernel._terms_t(leaves)):
-        for f, (_, rate, var) in enumerate(factors):
-            objective = objective + rate * g[c, f, 0] + var * g[c, f, 1]
-    return _grads_of(leaves, objective)
+    return _leaves_from_score(kernel, g.sum(0).cpu())
 
 
 def _sym_solve(chol, M):
@@ -190,12 +197,13 @@ def _add_grads(like, *parts):
 
 
 def overlap_add(n1, n2):
-    """Pair sites (n1 [M + 1, 2d], n2 [M + 1, 2d, 2d]) -> the chain's (lin [M, d], diag [M, d, d], sub [M - 1, d, d]) in
-    mfgm_sparse_theta's convention: site t + 1 starts at inducing state t, site t ends there; sub takes twice the lower-left block."""
+    """Pair sites (n1 [..., M + 1, 2d], n2 [..., M + 1, 2d, 2d]) -> the chain's (lin [..., M, d], diag [..., M, d, d],
+    sub [..., M - 1, d, d]) in mfgm_sparse_theta's convention: site t + 1 starts at inducing state t, site t ends there; sub takes
+    twice the lower-left block.  Leading axes (the panel's series) pass through."""
     d = n1.shape[-1] // 2
-    lin = n1[1:, :d] + n1[:-1, d:]
-    diag = n2[1:, :d, :d] + n2[:-1, d:, d:]
-    sub = 2.0 * n2[1:-1, d:, :d]
+    lin = n1[..., 1:, :d] + n1[..., :-1, d:]
+    diag = n2[..., 1:, :d, :d] + n2[..., :-1, d:, d:]
+    sub = 2.0 * n2[..., 1:-1, d:, :d]
     return lin, diag, sub
 
 
@@ -251,13 +259,7 @@ def conditional_part_native(kernel, plan, data, gap_lo, gap_hi, a, b, marg):
         plan.check_info()
     except ArithmeticError as e:
         raise ArithmeticError(_NOT_PD) from e
-    g = score.cpu()
-    leaves = kernel.hyperparameter_leaves("cpu")
-    objective = torch.zeros((), dtype=torch.float64)
-    for c, factors in enumerate(kernel._terms_t(leaves)):
-        for f, (_, rate, var) in enumerate(factors):
-            objective = objective + rate * g[c, f, 0] + var * g[c, f, 1]
-    return _grads_of(leaves, objective)
+    return _leaves_from_score(kernel, score.cpu())
 
 
 def sparse_native_route(model, data):
@@ -352,6 +354,102 @@ def sparse_elbo_grad(model, input_data, parts=None):
         bot = torch.cat([ext_s, ext_c[1:]], dim=-1)
         Sig_pair = torch.cat([top, bot], dim=-2)[idx]
         cond = conditional_part_torch(kernel, gap_lo, gap_hi, a, b, mu_pair, Sig_pair, idx, T)
+    if parts is not None:
+        parts["conditional"] = cond
+    return _add_grads(chain, chain, cond)
+
+
+# -- the panel's bound at fixed sites ---------------------------------------------------------------------------------
+def panel_native_route(model):
+    """Whether PanelSparseCVI.elbo_and_grad takes the HIP route: the model's fused passes apply and the chain part's score is native."""
+    return (model._native() and os.environ.get("VIDP_NATIVE_SPARSE_SCORE", "1") != "0"
+            and native_route(model._kernel, model.dist_p.plan))
+
+
+def conditional_part_panel_native(kernel, plan, data, gap_lo, gap_hi, a, b, packed):
+    """The conditional part of every series, summed, from one launch of mfgm_panel_cond_score on the packed marginals of the B-chain
+    plan (csrc/mfgm_panel_score.h)."""
+    import ctypes
+    from .kernels import _NOT_PD
+    from .packed import _ptr, _stream
+    lib = plan.lib
+    ws = data.get("score_ws")
+    if ws is None:
+        ws = data["score_ws"] = torch.empty(int(lib.mfgm_panel_cond_score_workspace_doubles(plan.B, data["n"])), dtype=torch.float64,
+                                            device=a.device)
+    score = torch.empty((8, 3, 2), dtype=torch.float64, device=a.device)
+    _lib.check(lib.mfgm_panel_cond_score(plan.h, ctypes.byref(data["struct"]), ctypes.byref(kernel._terms_struct(kernel._terms())),
+                                         _ptr(gap_lo), _ptr(gap_hi), _ptr(a), _ptr(b), _ptr(packed["x"]), _ptr(packed["Sig"]),
+                                         _ptr(packed["Sub"]), _ptr(score), _ptr(ws), _ptr(plan.info), _stream()), "mfgm_panel_cond_score")
+    try:
+        plan.check_info()
+    except ArithmeticError as e:
+        raise ArithmeticError(_NOT_PD) from e
+    return _leaves_from_score(kernel, score.cpu())
+
+
+def panel_elbo_grad(model, input_data, parts=None):
+    """Exact gradient of PanelSparseCVI.classic_elbo with respect to the shared kernel's hyper-parameters at fixed sites, summed over
+    the series (structure of hyperparameter_leaves(), CPU fp64): the decomposition of sparse_elbo_grad with a leading series axis,
+        dL = sum_b < eta_q - eta_p + F_b (g^_b - theta_s,b), d theta_p >  +  sum_{b,i} a_bi d fmu_bi + b_bi d fvar_bi  (q fixed).
+    The chain part is one batched score over the B chains on moments displaced by one batched Fisher-vector product; the conditional
+    part one launch of mfgm_panel_cond_score natively, autograd through `_parts` on at most model.CHUNK points at a time otherwise.
+    parts (a dict): receives chain_kl, chain_fisher and conditional separately."""
+    from . import tape
+    from .pair_sites import pair_marginals
+    kernel = model._kernel
+    z = model.inducing_inputs
+    data = model._data(input_data)
+    native = panel_native_route(model)
+    pl = model.dist_p.plan
+    B, T, d, n = pl.B, pl.T, pl.d, data["n"]
+    r = model._predict_lik(input_data)
+    g1, g2 = r["g1"].contiguous(), r["g2"].contiguous()             # exact zeros at the absent points
+    a, b = (g1 + 2.0 * g2 * r["fmu"]).contiguous(), g2
+    c = data.get("gaps")
+    if c is None:
+        _, lo, hi = interval_gaps(input_data[0].reshape(-1), z)
+        c = data["gaps"] = (lo.reshape(B, n).contiguous(), hi.reshape(B, n).contiguous())
+    gap_lo, gap_hi = c
+    w, idx = data["w"], data["idx"]
+    # ---- the CVI target g^ of every series (what update_sites accumulates at lr = 1 into zero sites) minus the sites, on the chains
+    if native:
+        import ctypes
+        from .packed import _ptr, _stream
+        t1, t2 = torch.zeros_like(model.nat1), torch.zeros_like(model.nat2)
+        _lib.check(pl.lib.mfgm_panel_site_update(ctypes.byref(data["struct"]), _ptr(g1), _ptr(g2), 1.0, _ptr(t1), _ptr(t2), _stream()),
+                   "mfgm_panel_site_update")
+    else:
+        t1, t2 = model._site_sums(data, g1, g2)
+    v_lin, v_diag, v_sub = overlap_add(t1 - model.nat1, t2 - model.nat2)
+    # ---- chain part: the score on (mu, Sig + delta_diag, Sub + delta_sub), delta = F (g^ - theta_s), every series at once
+    s = model._marginals()["packed"]
+    mu, cov, csub = pl.unpack(VEC, s["x"]), pl.unpack(SYM, s["Sig"]), pl.unpack(FULL, s["Sub"], T - 1)
+    _, th_diag, th_sub = model._theta()
+    _, dd, ds = tape.fisher_vector_product(pl, pl.unpack(SYM, th_diag), pl.unpack(FULL, th_sub, T - 1), mu, cov, csub, v_lin, v_diag, v_sub)
+    dts = (z[1:] - z[:-1])[None].expand(B, -1).contiguous()
+    score = score_native if native else score_fallback
+    displaced = dict(x=s["x"], Sig=pl.pack(SYM, cov + dd), Sub=pl.pack(FULL, csub + ds))
+    if parts is None:
+        chain = score(kernel, pl, dts, displaced)
+    else:
+        # the two brackets apart: the score is affine in the second moments, so F's share is a difference of two scores
+        parts["chain_kl"] = score(kernel, pl, dts, dict(x=s["x"], Sig=s["Sig"], Sub=s["Sub"]))
+        chain = score(kernel, pl, dts, displaced)
+        parts["chain_fisher"] = _add_grads(chain, chain, unflatten(chain, [-g for g in flatten(parts["chain_kl"])]))
+    # ---- conditional part
+    if native:
+        cond = conditional_part_panel_native(kernel, pl, data, gap_lo, gap_hi, a, b, s)
+    else:
+        pm, pc = pair_marginals(model, (mu, cov, csub))
+        cond = None
+        for lo in range(0, B, model._rows(n)):          # the pair covariances are gathered a block of series at a time
+            sl = slice(lo, lo + model._rows(n))
+            rows = torch.arange(pm[sl].shape[0], device=w.device)[:, None]
+            flat = lambda x: x[sl].reshape(-1)
+            part = conditional_part_torch(kernel, flat(gap_lo), flat(gap_hi), flat(a), flat(b), pm[sl][rows, idx[sl]].reshape(-1, 2 * d),
+                                          pc[sl][rows, idx[sl]].reshape(-1, 2 * d, 2 * d), flat(idx), T)
+            cond = part if cond is None else _add_grads(part, cond, part)
     if parts is not None:
         parts["conditional"] = cond
     return _add_grads(chain, chain, cond)

@@ -15,6 +15,9 @@ CPU tensors): the same quantities with batched torch ops -- on the device around
 tensors around a dense posterior over all inducing states of every series (small models, the host tests); the correctness anchor.
 The dense posterior, the pair marginals and the KL term are the functions of pair_sites.py, which the single-chain models call
 without the batch axis.
+
+The shared kernel is learned through elbo_and_grad (the exact gradient of the bound at fixed sites, summed over the series:
+hyper.panel_elbo_grad) and kernel_changed(), which is all KernelHyperTrainer needs of a model.
 """
 import ctypes
 import os
@@ -302,6 +305,13 @@ class PanelSparseCVI:
                                                   _ptr(self._nat2), _stream()), "mfgm_panel_site_update")
             self._version += 1
             return
+        s1, s2 = self._site_sums(data, r["g1"], r["g2"])
+        self.nat1 = (1 - lr) * self._nat1 + lr * s1      # (the setters move the stamps)
+        self.nat2 = (1 - lr) * self._nat2 + lr * s2
+
+    def _site_sums(self, data, g1, g2):
+        """sum over the points i in interval m of series b of (g1_i w_i, g2_i w_i w_i^T) with torch ops, in the shapes of the sites:
+        the CVI target of the torch route (update_sites, hyper.panel_elbo_grad)."""
         B, M1, d2, n = self.num_series, self._nat1.shape[1], self._nat1.shape[2], data["n"]
         w, idx = data["w"], data["idx"]
         s1 = torch.zeros_like(self._nat1).view(B * M1, d2)
@@ -310,10 +320,9 @@ class PanelSparseCVI:
             sl = slice(lo, lo + self._rows(n))
             flat = (idx[sl] + M1 * torch.arange(lo, lo + idx[sl].shape[0], device=idx.device)[:, None]).reshape(-1)
             ws = w[sl].reshape(-1, d2)
-            s1.index_add_(0, flat, r["g1"][sl].reshape(-1, 1) * ws)
-            s2.index_add_(0, flat, r["g2"][sl].reshape(-1, 1, 1) * ws[:, :, None] * ws[:, None, :])
-        self.nat1 = (1 - lr) * self._nat1 + lr * s1.view_as(self._nat1)      # (the setters move the stamps)
-        self.nat2 = (1 - lr) * self._nat2 + lr * s2.view_as(self._nat2)
+            s1.index_add_(0, flat, g1[sl].reshape(-1, 1) * ws)
+            s2.index_add_(0, flat, g2[sl].reshape(-1, 1, 1) * ws[:, :, None] * ws[:, None, :])
+        return s1.view_as(self._nat1), s2.view_as(self._nat2)
 
     def elbo_per_series(self, input_data):
         """[B]: sum_i E_q log p(y_bi | f_bi) - KL[q_b(s_Z) || p(s_Z)] of every series."""
@@ -333,7 +342,29 @@ class PanelSparseCVI:
         return -self.classic_elbo(input_data)
 
     def elbo_and_grad(self, input_data):
-        raise NotImplementedError("elbo_and_grad is not implemented for PanelSparseCVI: out of scope (DESIGN.md section 22)")
+        """(classic_elbo(input_data), its exact gradient with respect to the shared kernel's hyper-parameters with the sites of every
+        series held fixed, summed over the series): the gradient in the structure of kernel.hyperparameter_leaves(), CPU fp64 tensors,
+        as SparseCVIGaussianProcess.elbo_and_grad (hyper.panel_elbo_grad).  Device tensors, state dimension
+        <= 8; per-series gradients and the likelihood's own parameters are out of scope."""
+        from . import hyper
+        if not on_device(self):
+            raise NotImplementedError("elbo_and_grad needs the model on the device; on CPU tensors it is out of scope (DESIGN.md section 27)")
+        if self._kernel.state_dim > 8:
+            raise NotImplementedError(f"elbo_and_grad is not implemented for PanelSparseCVI with state dimension "
+                                      f"{self._kernel.state_dim} > 8: the batched wide Fisher-vector product is not built")
+        hyper.precheck(self._kernel)
+        elbo = self.classic_elbo(input_data)
+        return elbo, hyper.panel_elbo_grad(self, input_data)
+
+    def kernel_changed(self):
+        """The kernel's hyper-parameters were assigned: drop everything derived from them (the prior, its plan and naturals, the theta
+        and sweep buffers of that plan, the data cache with w and c, the marginal and prediction caches, the dense anchor of CPU
+        tensors).  The sites stay."""
+        self._dist_p, self._pn = None, None
+        self._marg, self._data_cache, self._pred_cache = None, None, None
+        self._dense_p, self._dense_q = None, None
+        self.__dict__.pop("_theta_bufs", None)
+        self.__dict__.pop("_sweep_bufs", None)
 
     @property
     def dist_q(self):

@@ -473,8 +473,9 @@ class KernelHyperTrainer:
     and notebooks do with `Adam.minimize(model.loss, model.trainable_variables)` -- for GaussianProcessRegression and the sites models
     (CVIGaussianProcess, PowerExpectationPropagation).  The gradient is the model's log_likelihood_and_grad() (one factorisation, one
     selected inverse, one score pass: hyper.py).  A model with elbo_and_grad(input_data)
-    (SparseCVIGaussianProcess) is trained on its negative ELBO at fixed sites instead and needs `input_data`,
-    which step() hands to elbo_and_grad and fit() to update_sites.
+    (SparseCVIGaussianProcess; PanelSparseCVI, whose gradient is summed over its series so that every series
+    informs the one shared kernel, section 27) is trained on its negative ELBO at fixed sites instead and needs `input_data`, which
+    step() hands to elbo_and_grad and fit() to update_sites.
 
     Adam (tf defaults, `_Adam`) runs on unconstrained values: softplus^-1 of the positive scalars (gpflow's default `positive()`;
     transform="log" is the other choice), the identity for the LEG kernel's N and R.  learn_noise=True (GPR with a scalar
