@@ -346,6 +346,24 @@ int mfgm_cq_selinv_girsanov_alt(const mfgm_plan* plan, int only_level, const mfg
 int mfgm_cq_selinv_kl(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L, const double* y,
                       const mfgm_sde_params* prm, double* Sig, double* x, double* kl_part, double* obs_mu, double* obs_cov, void* ws,
                       void* stream);
+/* mfgm_cq_factor_pair with a THINNED first factor (d <= 6).  Of (L, y) only the records of the kept nodes are written: a node at
+ * local step s of its level-0 segment of length R is kept iff s is even or s == R - 1.  No other element of L / y is touched (the
+ * arrays keep their size and layout), so about half of the first factor's bytes are neither written here nor read by the sweep that
+ * follows; (L2, y2), logdet / quad and the coarse levels are those of the full call, bit for bit, and so are the kept records.
+ * stride 0: the level-0 reduces of mfgm_cq_factor_pair (scratch may be NULL); otherwise those of mfgm_cq_factor_pair_heads, under
+ * its contract.  stage < 0: the whole call; 0 ... 3: that stage alone, as mfgm_cq_factor_pair_stage (logdet / quad are not written).
+ * Such a factor is read by mfgm_cq_selinv_kl_thin alone.  Returns 1 for d > 6 and whatever the full entries return 1 for. */
+int mfgm_cq_factor_pair_thin(const mfgm_plan* plan, int stage, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L,
+                             double* y, double* logdet, double* quad, double* L2, double* y2, double* scratch, size_t scratch_doubles, void* ws,
+                             int* info, void* stream);
+/* mfgm_cq_selinv_kl on the thinned factor (L, y) of mfgm_cq_factor_pair_thin, same arguments and outputs; only_level is handled as
+ * mfgm_cq_selinv_kl handles it.  The level-0 sweep rebuilds the record of every node that is not kept from the kept one before it by
+ * one step of the forward recursion, in registers.  CONTRACT: q must be the state the factor was made from -- dyn, the offsets and
+ * THE SITE SET (slot, site_lin, site_sym) unchanged since that call: a site on a rebuilt node enters its record.  The rebuilt records
+ * agree with the stored ones of the full factor to rounding, not bit for bit.  Returns 1 for d > 6. */
+int mfgm_cq_selinv_kl_thin(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L, const double* y,
+                           const mfgm_sde_params* prm, double* Sig, double* x, double* kl_part, double* obs_mu, double* obs_cov, void* ws,
+                           void* stream);
 /* mfgm_mvn_obs_ve on marginals already gathered in observation order (mu [B n_per, d], cov [B n_per, d, d]): ve [B, ceil(n_per/256)] */
 int mfgm_mvn_ve_compact(int B, int n_per, int d, const double* mu, const double* cov, const double* y, const double* Sinv, double cst,
                         double* ve, void* stream);

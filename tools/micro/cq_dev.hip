@@ -29,3 +29,14 @@ void inst_heads_all(SweepArgs a, CqArgs q, double* park) { inst_heads<6>(a, q, p
 void inst_pairs(SweepArgs a, CqArgs q) {
     inst_pair<1>(a, q); inst_pair<2>(a, q); inst_pair<3>(a, q); inst_pair<4>(a, q); inst_pair<5>(a, q); inst_pair<6>(a, q);
 }
+// the thinned pair route (mfgm_cq_factor_pair_thin, mfgm_cq_selinv_kl_thin) at every size and cache policy the library dispatches it for
+template <int D>
+void inst_thin(SweepArgs a, CqArgs q, SdeParams pr) {
+    hipLaunchKernelGGL((k_forward_pair_thin_cq<D>), dim3(1), dim3(128), 0, 0, a, q, a, q);
+    hipLaunchKernelGGL((k_forward_pair_thin_cq<D, 1>), dim3(1), dim3(128), 0, 0, a, q, a, q);
+    hipLaunchKernelGGL((k_backward_kl_thin_cq<D>), dim3(1), dim3(64), 0, 0, a, pr, q);
+    hipLaunchKernelGGL((k_backward_kl_thin_cq<D, 2>), dim3(1), dim3(64), 0, 0, a, pr, q);
+}
+void inst_thin_all(SweepArgs a, CqArgs q, SdeParams pr) {
+    inst_thin<1>(a, q, pr); inst_thin<2>(a, q, pr); inst_thin<3>(a, q, pr); inst_thin<4>(a, q, pr); inst_thin<5>(a, q, pr); inst_thin<6>(a, q, pr);
+}

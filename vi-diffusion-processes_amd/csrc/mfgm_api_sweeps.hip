@@ -401,7 +401,9 @@ int cq_factor_impl(const Plan& P0, const CqArgs& q, double* Lg, double* yg, doub
 // the separator marginals of their factorisation in place.  Every body is the one the single route runs: same numbers.
 template <int D>
 int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double* Lg, double* yg, double* logdet, double* quad, double* L2,
-                        double* y2, double* ws, int* info, hipStream_t st, int only_stage = -1, double* park = nullptr, int stride = 0) {
+                        double* y2, double* ws, int* info, hipStream_t st, int only_stage = -1, double* park = nullptr, int stride = 0,
+                        bool thin = false) {
+    // thin (mfgm_cq_factor_pair_thin, d <= 6): (Lg, yg) receives the records of the kept nodes only; (L2, y2) is full either way
     // park (mfgm_cq_factor_pair_heads): the two level-0 reduces share the elimination of everything but the observed nodes
     // only_stage (profiling): 0 the two level-0 reduces, 1 the level-0 forward pair, 2 the joint up phase of the levels above, 3 their
     // joint backward pass
@@ -436,8 +438,13 @@ int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double
     if (!on(1)) {
         // (profiling call for another stage)
     } else if constexpr (D <= 6) {
-        if (a0.lv.nt >= 1) hipLaunchKernelGGL((k_forward_pair_cq<D, 1>), grid, dim3(128), 0, st, a0, q, a1, q2);
-        else hipLaunchKernelGGL((k_forward_pair_cq<D>), grid, dim3(128), 0, st, a0, q, a1, q2);
+        const dim3 pair(128);
+        const bool nt1 = a0.lv.nt >= 1;
+        if (thin) {
+            if (nt1) hipLaunchKernelGGL((k_forward_pair_thin_cq<D, 1>), grid, pair, 0, st, a0, q, a1, q2);
+            else hipLaunchKernelGGL((k_forward_pair_thin_cq<D>), grid, pair, 0, st, a0, q, a1, q2);
+        } else if (nt1) hipLaunchKernelGGL((k_forward_pair_cq<D, 1>), grid, pair, 0, st, a0, q, a1, q2);
+        else hipLaunchKernelGGL((k_forward_pair_cq<D>), grid, pair, 0, st, a0, q, a1, q2);
         MFGM_CHECK_LAUNCH();
     } else {
         // d = 7, 8: the body does not fit 256 registers; one forward sweep after the other
@@ -480,7 +487,8 @@ int cq_selinv_girsanov_impl(const Plan& P, const CqArgs& q, const double* Lg, co
 
 template <int D>
 int cq_selinv_kl_impl(const Plan& P, const CqArgs& q, const double* Lg, const double* yg, const SdeParams& pr, double* Sig, double* x,
-                      double* kl, double* ws, hipStream_t st, int only_level) {
+                      double* kl, double* ws, hipStream_t st, int only_level, bool thin = false) {
+    if (thin && D > 6) return 1;                     // no sweep reads a thinned factor at d = 7, 8: refused before anything is launched
     if (only_level != 0)
         if (int rc = coarse_down<D>(P, ws, true, st)) return rc;
     if (only_level > 0) return 0;                    // profiling: the levels above the finest one alone
@@ -491,8 +499,16 @@ int cq_selinv_kl_impl(const Plan& P, const CqArgs& q, const double* Lg, const do
     a.Sigg = Sig; a.mug = x;
     a.part = ws + P.off_part[0];
     bind_up(P, 0, ws, a);
-    if (a.lv.nt >= 2) hipLaunchKernelGGL((k_backward_kl_cq<D, 2>), dim3(a.lv.Lpad / 64), dim3(64), 0, st, a, pr, q);
-    else hipLaunchKernelGGL((k_backward_kl_cq<D>), dim3(a.lv.Lpad / 64), dim3(64), 0, st, a, pr, q);
+    const dim3 grid(a.lv.Lpad / 64), block(64);
+    if (thin) {
+        // (Lg, yg) holds the kept records only (mfgm_cq_factor_pair_thin): the sweep that rebuilds the others
+        if constexpr (D <= 6) {
+            a.aD = -2.0; a.aR = 1.0;                 // the forward step that rebuilds a record takes the factorisation's scales
+            if (a.lv.nt >= 2) hipLaunchKernelGGL((k_backward_kl_thin_cq<D, 2>), grid, block, 0, st, a, pr, q);
+            else hipLaunchKernelGGL((k_backward_kl_thin_cq<D>), grid, block, 0, st, a, pr, q);
+        }
+    } else if (a.lv.nt >= 2) hipLaunchKernelGGL((k_backward_kl_cq<D, 2>), grid, block, 0, st, a, pr, q);
+    else hipLaunchKernelGGL((k_backward_kl_cq<D>), grid, block, 0, st, a, pr, q);
     MFGM_CHECK_LAUNCH();
     return sum_level0_partials(P, ws, 0, kl, nullptr, st);
 }
@@ -785,6 +801,30 @@ int mfgm_cq_factor_pair_heads_stage(const mfgm_plan* plan, int stage, int stride
     const CqArgs c = cq_args(q), c2 = cq_args(q_next);
     MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, nullptr, nullptr, L2, y2, (double*)ws, info, (hipStream_t)stream, stage,
                                                   scratch, stride)));
+}
+
+int mfgm_cq_factor_pair_thin(const mfgm_plan* plan, int stage, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next,
+                             double* L, double* y, double* logdet, double* quad, double* L2, double* y2, double* scratch, size_t scratch_doubles,
+                             void* ws, int* info, void* stream) {
+    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info) || plan->p.d > 6 || stage < -1 || stage > 3) return 1;
+    if (stride != 0 && !cq_heads_ok(plan, stride, scratch, scratch_doubles)) return 1;
+    const Plan& P = plan->p;
+    const CqArgs c = cq_args(q), c2 = cq_args(q_next);
+    if (stage >= 0) logdet = quad = nullptr;
+    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, logdet, quad, L2, y2, (double*)ws, info, (hipStream_t)stream, stage,
+                                                  stride ? scratch : nullptr, stride, true)));
+}
+
+int mfgm_cq_selinv_kl_thin(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L, const double* y,
+                           const mfgm_sde_params* prm, double* Sig, double* x, double* kl_part, double* obs_mu, double* obs_cov, void* ws,
+                           void* stream) {
+    if (!cq_ok(plan, q) || !L || !y || !prm || !kl_part || !ws || prm->kind != 0 || plan->p.d > 6) return 1;
+    if ((obs_mu != nullptr) != (obs_cov != nullptr) || (Sig != nullptr) != (x != nullptr)) return 1;
+    const Plan& P = plan->p;
+    const SdeParams pr = sde_params(prm);
+    CqArgs c = cq_args(q);
+    c.obs_mu = obs_mu; c.obs_cov = obs_cov;
+    MFGM_DISPATCH_D(P.d, (cq_selinv_kl_impl<DD>(P, c, L, y, pr, Sig, x, kl_part, (double*)ws, (hipStream_t)stream, only_level, true)));
 }
 
 int mfgm_cq_selinv_girsanov_alt(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L2, const double* y2,

@@ -643,7 +643,9 @@ MFGM_DEV void backward_p_step(const double (&Pm)[MFGM_NTRI(D)], const double (&s
 #ifndef MFGM_CQ_SYNC_EVERY
 #define MFGM_CQ_SYNC_EVERY 2       // nodes between the barriers of k_forward_reduce_cq's two wavefronts (a power of two)
 #endif
-template <int D, bool SYNC>
+// THIN: the factor record of a node is stored only where cq_kept says so (k_forward_pair_thin_cq below); nothing else changes.
+MFGM_DEV bool cq_kept(int s, int R) { return !(s & 1) || s == R - 1; }
+template <int D, bool SYNC, bool THIN = false>
 MFGM_DEV void forward_cq_body(const SweepArgs& a, const CqArgs& q, const int lane, const LaneRef me) {
     constexpr int ET = MFGM_NTRI(D), EF = D * D, E3 = 3 * D;
     const int P = a.lv.P, R = a.lv.R, Lp = a.lv.Lpad, n = a.lv.n;
@@ -750,6 +752,9 @@ MFGM_DEV void forward_cq_body(const SweepArgs& a, const CqArgs& q, const int lan
                 }
                 if (sites && s + 2 < len) sB = cq_slot(q.slot, R, s + 2, me);
             }
+            // (cq_forward_step below restates this step -- the carry, the F / h assembly above and what follows down to z -- for
+            //  k_backward_kl_thin_cq, the same calls in the same order: an edit here belongs there too, or the records that sweep
+            //  rebuilds no longer round as the stored ones do)
             double invd[D];
             chol_inplace<D>(F, invd, bad);
             trsv_lower<D>(F, invd, h);
@@ -769,8 +774,10 @@ MFGM_DEV void forward_cq_body(const SweepArgs& a, const CqArgs& q, const int lan
                 for (int k = i; k < D; ++k) t = __builtin_fma(X[tix(k, i)], h[k], t);
                 z[i] = t;
             }
-            st_node<ET>(a.Lg, R, s, me, Pm);
-            st_node<D>(a.yg, R, s, me, z);
+            if (!THIN || cq_kept(s, R)) {
+                st_node<ET>(a.Lg, R, s, me, Pm);
+                st_node<D>(a.yg, R, s, me, z);
+            }
             // carried to the next node: C = (aS S) P (aS S)^T, c = (aS S) z with S = diag(theta_sub) + sOff (1 1^T - I)
             cq_carry<D>(Pm, z, sdn, has_next ? a.aS : 0.0, q.sOff, C, c);
         }
@@ -995,6 +1002,19 @@ static __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2
     const int lane = min((int)blockIdx.x * 64 + l, a.lv.L - 1);
     const LaneRef me{(int)blockIdx.x, lane & 63, NT >= 1 ? 1 : 0};     // streamed stores only: the second reader of a record is served from the cache
     if (wave == 0) forward_cq_body<D, true>(a, q, lane, me);
+    else forward_cq_body<D, true>(a2, q2, lane, me);
+}
+// The same with a THINNED first factor (mfgm_cq_factor_pair_thin): wavefront 0 stores the records of the kept nodes only -- even local
+// steps and step R - 1, cq_kept -- and touches no other record, so whole cache lines of (Lg, yg) drop out of the sweep's writes.
+// Everything else (logdet, quad, the carry, the barriers, the second factor) is forward_cq_body as it is; k_backward_kl_thin_cq
+// rebuilds the missing records in registers (cq_forward_step).
+template <int D, int NT = 0>
+static __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_forward_pair_thin_cq(SweepArgs a, CqArgs q, SweepArgs a2,
+                                                                                                                 CqArgs q2) {
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int lane = min((int)blockIdx.x * 64 + l, a.lv.L - 1);
+    const LaneRef me{(int)blockIdx.x, lane & 63, NT >= 1 ? 1 : 0};
+    if (wave == 0) forward_cq_body<D, true, true>(a, q, lane, me);
     else forward_cq_body<D, true>(a2, q2, lane, me);
 }
 
@@ -1300,6 +1320,174 @@ static __global__ __launch_bounds__(64) void k_backward_kl_cq(SweepArgs a, SdePa
         acc += kl_transition<D>(pr, m, v, c, xn, vn);
     } else {
         // node 0: 1/2 [ tr(P0^{-1} Sigma_0) + (m0 - mu0)^T P0^{-1} (m0 - mu0) + logdet P0 ]
+        double tr = 0.0, mh = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            double pm = 0.0;
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                pm = __builtin_fma(pr.P0inv[six(i, j)], xn[j] - pr.mu0[j], pm);
+                tr = __builtin_fma(pr.P0inv[six(i, j)], Sn[six(i, j)], tr);
+            }
+            mh = __builtin_fma(pm, xn[i] - pr.mu0[i], mh);
+        }
+        acc += 0.5 * (tr + mh + pr.logdetP0);
+    }
+    a.part[lane] = acc;
+}
+
+// ---- backward KL sweep on a THINNED factor (k_forward_pair_thin_cq) ---------------------------------------------------------------------
+// The factor record (P_s, z_s) of an odd local step s < R - 1 is not in the arrays.  The forward recursion gives it from record s - 1
+// -- which a backward sweep holds anyway, one step ahead -- diag theta_sub of node s - 1 and theta_lin / diag theta_diag / the site of
+// node s, so the sweep walks its nodes in pairs (s odd, s - 1): one forward step rebuilds record s in registers, the backward step
+// at s uses it, the records of the next pair are requested, and the backward step at s - 1 runs on the record already held.
+//
+// One step of forward_cq_body's loop, the same calls in the same order (that body is left as it is so that every kernel built on it
+// keeps its code: the two are edited together).  Pp, zp: record s - 1; sdp: diag theta_sub of node s - 1; lin, dg: theta_lin and diag
+// theta_diag of node s; cnt, sl: 1 and the site's linear part when node s carries an observation, else 0.  The not-PD flag is the
+// forward sweep's to raise, not this one's.
+template <int D>
+MFGM_DEV void cq_forward_step(const double (&Pp)[MFGM_NTRI(D)], const double (&zp)[D], const double (&sdp)[D], const double (&lin)[D],
+                              const double (&dg)[D], double dOff, double sOff, double aD, double aS, double aR, double cnt,
+                              const double (&ssym)[MFGM_NTRI(D)], const double (&sl)[D], double (&Pm)[MFGM_NTRI(D)], double (&z)[D]) {
+    constexpr int ET = MFGM_NTRI(D);
+    double C[ET], c[D], F[ET], h[D], invd[D], X[ET];
+    int bad = 0;
+    cq_carry<D>(Pp, zp, sdp, aS, sOff, C, c);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            const double dn = __builtin_fma(cnt, ssym[tix(i, j)], (i == j) ? dg[i] : dOff);
+            F[tix(i, j)] = __builtin_fma(aD, dn, -C[tix(i, j)]);
+        }
+#pragma unroll
+    for (int e = 0; e < D; ++e) h[e] = __builtin_fma(aR, lin[e] + sl[e], -c[e]);
+    chol_inplace<D>(F, invd, bad);
+    trsv_lower<D>(F, invd, h);
+    tri_inverse<D>(F, invd, X);
+    tri_t_tri<D>(X, Pm);
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = i; k < D; ++k) t = __builtin_fma(X[tix(k, i)], h[k], t);
+        z[i] = t;
+    }
+}
+
+// k_backward_kl_cq on a thinned factor.  q must carry the site set the factor was made with (slot, site_lin, site_sym): a site on a
+// rebuilt node enters its record.  The visits run from `top` = len - 2 down to 0; the loop is over the EVEN steps e, an iteration
+// visiting e + 1 first where that node is one to visit (always, but for the first iteration when top is even).
+template <int D, int NT = 0>
+static __global__ __launch_bounds__(64) void k_backward_kl_thin_cq(SweepArgs a, SdeParams pr, CqArgs q) {
+    constexpr int ET = MFGM_NTRI(D), EF = D * D, E3 = 3 * D;
+    const int lane = blockIdx.x * 64 + threadIdx.x;
+    if (lane >= a.lv.L) return;
+    const LaneRef me{(int)blockIdx.x, (int)threadIdx.x, NT};
+    const int P = a.lv.P, R = a.lv.R, n = a.lv.n;
+    const int b = lane / P, p = lane - b * P;
+    const int len = min(R, n - p * R);
+    const int se = len - 1, top = len - 2;
+    const int uP = a.up.P, uR = a.up.R;
+    const bool sites = (q.slot != nullptr);
+    const bool obs = (sites && q.obs_mu != nullptr);
+    double acc = 0.0;
+    double ssym[ET];
+    cq_site_sym<ET>(q, sites, ssym);
+
+    double Sn[ET], xn[D];
+    {
+        const int ul = b * uP + p / uR, us = p % uR;
+        ld_node<ET, true>(a.uSig, uR, us, LaneRef::of(ul), Sn);
+        ld_node<D, true>(a.umu, uR, us, LaneRef::of(ul), xn);
+    }
+    const bool keep = (a.Sigg != nullptr);
+    if (keep) {
+        st_node<ET>(a.Sigg, R, se, me, Sn);
+        st_node<D>(a.mug, R, se, me, xn);
+    }
+    if (obs) cq_store_obs<D>(q, cq_slot(q.slot, R, se, me), xn, Sn);
+
+    // one backward step, as in k_backward_kl_cq's loop: x holds z_s on entry
+    const auto visit = [&](int s, const double (&Pm)[ET], const double (&Gd)[D], double (&x)[D], int sc) {
+        double Ssub[EF], Sig[ET];
+        backward_p_step<D>(Pm, Gd, q.sOff, a.aS, Sn, xn, Sig, Ssub, x);
+        if (keep) {
+            st_node<D>(a.mug, R, s, me, x);
+            st_node<ET>(a.Sigg, R, s, me, Sig);
+        }
+        if (obs) cq_store_obs<D>(q, sc, x, Sig);
+        double v[D], c[D], vn[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) { v[i] = Sig[tix(i, i)]; c[i] = Ssub[i * D + i]; vn[i] = Sn[tix(i, i)]; }
+        acc += kl_transition<D>(pr, x, v, c, xn, vn);
+#pragma unroll
+        for (int i = 0; i < D; ++i) xn[i] = x[i];
+#pragma unroll
+        for (int e = 0; e < ET; ++e) Sn[e] = Sig[e];
+    };
+
+    // requested one step ahead: the record of the even node e (Ln, yn, diag theta_sub, slot) and, of the odd node above it, what the
+    // forward step and the visit need (theta_lin, diag theta_diag, diag theta_sub, slot)
+    double Ln[ET], Gdn[D], yn[D], lo[D], dgo[D], Gdo[D];
+    int sn = -1, so = -1;
+    if (len > 1) {
+        const int e0 = top & ~1;
+        ld_node<ET>(a.Lg, R, e0, me, Ln);
+        ld_part<E3, 2 * D, D>(q.dyn, R, e0, me, Gdn);
+        ld_node<D>(a.yg, R, e0, me, yn);
+        if (obs) sn = cq_slot(q.slot, R, e0, me);
+        if (top & 1) {
+            ld_part<E3, 0, D>(q.dyn, R, top, me, lo);
+            ld_part<E3, D, D>(q.dyn, R, top, me, dgo);
+            ld_part<E3, 2 * D, D>(q.dyn, R, top, me, Gdo);
+            if (sites) so = cq_slot(q.slot, R, top, me);
+        }
+    }
+    for (int e = (R - 2) & ~1; e >= 0; e -= 2) {
+        if (e <= top) {
+            double Lt[ET], z[D], Gd[D];
+#pragma unroll
+            for (int k = 0; k < ET; ++k) Lt[k] = Ln[k];
+#pragma unroll
+            for (int k = 0; k < D; ++k) { Gd[k] = Gdn[k]; z[k] = yn[k]; }
+            const int sc = sn;
+            if (e + 1 <= top) {
+                double Po[ET], x[D], sl[D];
+#pragma unroll
+                for (int i = 0; i < D; ++i) sl[i] = 0.0;
+                if (so >= 0) {
+#pragma unroll
+                    for (int i = 0; i < D; ++i) sl[i] = q.site_lin[(size_t)so * D + i];
+                }
+                cq_forward_step<D>(Lt, z, Gd, lo, dgo, q.dOff, q.sOff, a.aD, a.aS, a.aR, (so >= 0) ? 1.0 : 0.0, ssym, sl, Po, x);
+                visit(e + 1, Po, Gdo, x, so);
+            }
+            if (e > 0) {
+                ld_node<ET>(a.Lg, R, e - 2, me, Ln);
+                ld_part<E3, 2 * D, D>(q.dyn, R, e - 2, me, Gdn);
+                ld_node<D>(a.yg, R, e - 2, me, yn);
+                if (obs) sn = cq_slot(q.slot, R, e - 2, me);
+                ld_part<E3, 0, D>(q.dyn, R, e - 1, me, lo);
+                ld_part<E3, D, D>(q.dyn, R, e - 1, me, dgo);
+                ld_part<E3, 2 * D, D>(q.dyn, R, e - 1, me, Gdo);
+                if (sites) so = cq_slot(q.slot, R, e - 1, me);
+            }
+            visit(e, Lt, Gd, z, sc);
+        }
+    }
+    if (p > 0) {
+        // (record R - 1 of the segment on the left is a kept one)
+        const LaneRef left = LaneRef::of(lane - 1);
+        double Gd[D], Ssub[EF];
+        backward_s_left_cq<D>(a, q, R, left, Sn, Gd, Ssub);
+        double m[D], v[D], c[D], vn[D];
+        up_moments<D>(a, b, p - 1, m, v);
+#pragma unroll
+        for (int i = 0; i < D; ++i) { c[i] = -Ssub[i * D + i]; vn[i] = Sn[tix(i, i)]; }
+        acc += kl_transition<D>(pr, m, v, c, xn, vn);
+    } else {
         double tr = 0.0, mh = 0.0;
 #pragma unroll
         for (int i = 0; i < D; ++i) {

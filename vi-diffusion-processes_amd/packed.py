@@ -130,6 +130,7 @@ class Plan:
         if r is not None:
             y = out.get("y") if out.get("y") is not None else self.empty(VEC)
         self.epoch += 1
+        out["thin"] = False      # (a buffer dict says whether the factor it holds is a thinned one: cq_factor_pair)
         logdet = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
         quad = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_quad else None
         _lib.check(self.lib.mfgm_packed_factor_form(self.h, form, _ptr(D), _ptr(S), _ptr(r), float(aD), float(aS), float(aR),
@@ -146,6 +147,7 @@ class Plan:
         G = out.get("G") if out.get("G") is not None else self.empty(FULL)
         y = out.get("y") if out.get("y") is not None else self.empty(VEC)
         self.epoch += 1
+        out["thin"] = False
         logdet = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
         if packed:
             _lib.check(self.lib.mfgm_sparse_factor_q(self.h, -1, _ptr(nat1), _ptr(nat2), _ptr(plin), _ptr(pdiag), _ptr(psub), _ptr(L), _ptr(G),
@@ -486,6 +488,7 @@ class Plan:
         if not use_ahead and next_sites is None:
             _lib.check(self.lib.mfgm_cq_factor(self.h, ctypes.byref(cq.struct()), _ptr(L), _ptr(y), _ptr(logdet), None, _ptr(self.ws),
                                                _ptr(self.info), _stream()), "mfgm_cq_factor")
+            out["thin"] = False      # (the buffer's marker, cq_factor_pair: what it holds now is a full factor)
             return dict(L=L, y=y, logdet=logdet)
         nxt = None
         if next_sites is not None:
@@ -495,16 +498,22 @@ class Plan:
                                                      _ptr(self.info), 1 if use_ahead else 0, ctypes.byref(nxt) if nxt is not None else None,
                                                      ctypes.c_void_p(side.cuda_stream) if side is not None else None, _stream()),
                    "mfgm_cq_factor_pipelined")
+        out["thin"] = False
         return dict(L=L, y=y, logdet=logdet)
 
-    def cq_factor_pair(self, cq, next_sites, out=None, out2=None, want_logdet=True, head_stride=None):
+    def cq_factor_pair(self, cq, next_sites, out=None, out2=None, want_logdet=True, head_stride=None, thin=False):
         """Two factorisations of one dyn in one call (mfgm_cq_factor_pair): that of `cq` -> dict(L, y, logdet) and that of the same
         state with the observation sites `next_sites` = (site_lin, site_sym) -> the second dict(L, y).  The levels above the finest one
         run once at double width; both coarse backward passes are made, so the sweeps that follow take only_level=0:
         cq_selinv_kl on the first, cq_selinv_girsanov(alt=True) on the second.
         head_stride: every observation sits at a local step of its segment that is a multiple of it (the caller's word); the level-0
         reduces then share the elimination of everything but the observed nodes (mfgm_cq_factor_pair_heads; the plan keeps the
-        scratch array)."""
+        scratch array).
+        thin (d <= 6): the first factor holds the records of the kept nodes only -- even local steps and the last one of a level-0
+        segment (mfgm_cq_factor_pair_thin) -- and cq_selinv_kl, told so, rebuilds the others.  The marker: the first dict returned
+        then carries thin=True (the dict of a full factor holds its arrays and nothing else, as every caller that walks one
+        expects: no marker means full), and the buffer dicts `out` / `out2` always say thin=True / False for what they hold now --
+        every producer that writes into a buffer sets it.  Whoever reads (L, y) later passes the marker on."""
         out = {} if out is None else out
         out2 = {} if out2 is None else out2
         L = out.get("L") if out.get("L") is not None else self.empty(TRI)
@@ -515,15 +524,24 @@ class Plan:
         logdet = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
         nxt = cq.struct()
         nxt.site_lin, nxt.site_sym = next_sites[0].data_ptr(), next_sites[1].data_ptr()
-        if head_stride is not None:
-            scratch = self._heads_scratch(int(head_stride))
+        scratch = self._heads_scratch(int(head_stride)) if head_stride is not None else None
+        if thin:
+            _lib.check(self.lib.mfgm_cq_factor_pair_thin(self.h, -1, 0 if head_stride is None else int(head_stride), ctypes.byref(cq.struct()),
+                                                         ctypes.byref(nxt), _ptr(L), _ptr(y), _ptr(logdet), None, _ptr(L2), _ptr(y2), _ptr(scratch),
+                                                         0 if scratch is None else scratch.numel(), _ptr(self.ws), _ptr(self.info), _stream()),
+                       "mfgm_cq_factor_pair_thin")
+        elif head_stride is not None:
             _lib.check(self.lib.mfgm_cq_factor_pair_heads(self.h, int(head_stride), ctypes.byref(cq.struct()), ctypes.byref(nxt), _ptr(L), _ptr(y),
                                                           _ptr(logdet), None, _ptr(L2), _ptr(y2), _ptr(scratch), scratch.numel(), _ptr(self.ws),
                                                           _ptr(self.info), _stream()), "mfgm_cq_factor_pair_heads")
-            return dict(L=L, y=y, logdet=logdet), dict(L=L2, y=y2)
-        _lib.check(self.lib.mfgm_cq_factor_pair(self.h, ctypes.byref(cq.struct()), ctypes.byref(nxt), _ptr(L), _ptr(y), _ptr(logdet), None,
-                                                _ptr(L2), _ptr(y2), _ptr(self.ws), _ptr(self.info), _stream()), "mfgm_cq_factor_pair")
-        return dict(L=L, y=y, logdet=logdet), dict(L=L2, y=y2)
+        else:
+            _lib.check(self.lib.mfgm_cq_factor_pair(self.h, ctypes.byref(cq.struct()), ctypes.byref(nxt), _ptr(L), _ptr(y), _ptr(logdet), None,
+                                                    _ptr(L2), _ptr(y2), _ptr(self.ws), _ptr(self.info), _stream()), "mfgm_cq_factor_pair")
+        out["thin"], out2["thin"] = bool(thin), False
+        first = dict(L=L, y=y, logdet=logdet)
+        if thin:
+            first["thin"] = True
+        return first, dict(L=L2, y=y2)
 
     def _heads_scratch(self, stride):
         """The array mfgm_cq_factor_pair_heads parks its shared part in, kept from call to call (one stride per plan in practice).
@@ -534,24 +552,29 @@ class Plan:
             held = self._heads_buf = (stride, torch.empty(max(int(n), 1), dtype=torch.float64, device=self.device))
         return held[1]
 
-    def cq_selinv_girsanov(self, cq, L, y, prm, dyn_out, only_level=-1, alt=False):
-        """alt: (L, y) is the second factorisation of cq_factor_pair (its coarse levels are the workspace's second copy)."""
+    def cq_selinv_girsanov(self, cq, L, y, prm, dyn_out, only_level=-1, alt=False, thin=False):
+        """alt: (L, y) is the second factorisation of cq_factor_pair (its coarse levels are the workspace's second copy).
+        thin: the marker of the factor (L, y); this sweep has no form that reads a thinned one."""
+        if thin:
+            raise ValueError("cq_selinv_girsanov: a thinned factor is read by cq_selinv_kl alone")
         fn = self.lib.mfgm_cq_selinv_girsanov_alt if alt else self.lib.mfgm_cq_selinv_girsanov
         _lib.check(fn(self.h, int(only_level), ctypes.byref(cq.struct()), _ptr(L), _ptr(y), ctypes.byref(prm),
                       _ptr(dyn_out), _ptr(self.ws), _stream()), "mfgm_cq_selinv_girsanov_alt" if alt else "mfgm_cq_selinv_girsanov")
         return dyn_out
 
-    def cq_selinv_kl(self, cq, L, y, prm, out=None, obs_mu=None, obs_cov=None, only_level=-1, want_marginals=True):
+    def cq_selinv_kl(self, cq, L, y, prm, out=None, obs_mu=None, obs_cov=None, only_level=-1, want_marginals=True, thin=False):
         """want_marginals=False: the marginal arrays are not written (Sig, x = None in the result); the KL sum and the marginals at
-        the observation nodes are all the ELBO needs."""
+        the observation nodes are all the ELBO needs.
+        thin: the marker of the factor (L, y) (cq_factor_pair); `cq` must then still carry the sites the factor was made with."""
         out = {} if out is None else out
         Sig = x = None
         if want_marginals:
             Sig = out.get("Sig") if out.get("Sig") is not None else self.empty(SYM)
             x = out.get("x") if out.get("x") is not None else self.empty(VEC)
         kl = torch.empty(self.B, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.mfgm_cq_selinv_kl(self.h, int(only_level), ctypes.byref(cq.struct()), _ptr(L), _ptr(y), ctypes.byref(prm), _ptr(Sig),
-                                              _ptr(x), _ptr(kl), _ptr(obs_mu), _ptr(obs_cov), _ptr(self.ws), _stream()), "mfgm_cq_selinv_kl")
+        fn, name = (self.lib.mfgm_cq_selinv_kl_thin, "mfgm_cq_selinv_kl_thin") if thin else (self.lib.mfgm_cq_selinv_kl, "mfgm_cq_selinv_kl")
+        _lib.check(fn(self.h, int(only_level), ctypes.byref(cq.struct()), _ptr(L), _ptr(y), ctypes.byref(prm), _ptr(Sig),
+                      _ptr(x), _ptr(kl), _ptr(obs_mu), _ptr(obs_cov), _ptr(self.ws), _stream()), name)
         return dict(Sig=Sig, x=x, klpart=kl)
 
     def mvn_ve_compact(self, mu, cov, n_per, y, Sinv, cst, partials=False):

@@ -692,6 +692,9 @@ class CVISitesSDE(CVISitesSSM):
     # observations sit on a regular grid through the origin and the segment length is a multiple of its spacing; by default such a
     # model eliminates the unobserved nodes once for both (mfgm_cq_factor_pair_heads; A/B in DESIGN.md 5d)
     pair_heads = os.environ.get("VIDP_PAIR_HEADS", "1") != "0"
+    # VIDP_THIN_FACTOR=0: the pair route stores the whole first factor.  By default (d <= 6) it stores the records of every other node
+    # and the KL sweep rebuilds the rest in registers (mfgm_cq_factor_pair_thin / mfgm_cq_selinv_kl_thin; A/B in DESIGN.md 5d)
+    thin_factor = os.environ.get("VIDP_THIN_FACTOR", "1") != "0"
     # below this many nodes (B T) a level-0 reduce is a few microseconds: the second stream's event round trips would cost more than
     # they hide (config 1, T = 1001: 0.133 -> 0.174 ms with it)
     pipeline_min_nodes = 200000
@@ -788,8 +791,8 @@ class CVISitesSDE(CVISitesSSM):
                     if pair:
                         # the WHOLE first factorisation of the next step with this one: the coarse levels of both in one chain
                         f, f2 = pl.cq_factor_pair(cq, (lin, sym), out=self._bufs["f"], out2=self._bufs.setdefault("f2", {}),
-                                                  head_stride=self._pair_head_stride())
-                        self._bufs["f2"].update(L=f2["L"], y=f2["y"])
+                                                  head_stride=self._pair_head_stride(), thin=self.thin_factor and self.state_dim <= 6)
+                        self._bufs["f2"].update(L=f2["L"], y=f2["y"], thin=f2.get("thin", False))
                         return f, f2
                     return pl.cq_factor(cq, want_logdet=True, out=self._bufs["f"], next_sites=(lin, sym), side=ahead.side)
                 f = ahead.make(self._data_nat1, cq, pl, launch, kind=ahead.PAIR if pair else ahead.REDUCE)
@@ -797,9 +800,10 @@ class CVISitesSDE(CVISitesSSM):
             else:
                 f = pl.cq_factor(cq, want_logdet=True, out=self._bufs["f"], use_ahead=ahead.take(self._data_nat1, cq, pl), side=ahead.side)
                 coarse_done = False
-            self._bufs["f"].update(L=f["L"], y=f["y"])
+            self._bufs["f"].update(L=f["L"], y=f["y"], thin=f.get("thin", False))
             s = pl.cq_selinv_kl(cq, f["L"], f["y"], self._sde_prm, out=self._bufs["s"], obs_mu=self.fx_mus_obs if obs else None,
-                                obs_cov=self.fx_covs_obs if obs else None, want_marginals=not lazy, only_level=0 if coarse_done else -1)
+                                obs_cov=self.fx_covs_obs if obs else None, want_marginals=not lazy, only_level=0 if coarse_done else -1,
+                                thin=f.get("thin", False))
             if not lazy:
                 self._bufs["s"].update(Sig=s["Sig"], x=s["x"])
             self._q = dict(logdetL=f["logdet"], mu=s["x"], Sig=s["Sig"], Sub=None, mom=None, klpart=s["klpart"], epoch=pl.epoch)
@@ -812,7 +816,7 @@ class CVISitesSDE(CVISitesSSM):
                 f = pl.cq_factor(cq, want_logdet=False, out=self._bufs["f"])
                 self._q["epoch"] = pl.epoch
             s = pl.cq_selinv_kl(cq, f["L"], f["y"], self._sde_prm, out=self._bufs["s"], obs_mu=self.fx_mus_obs if obs else None,
-                                obs_cov=self.fx_covs_obs if obs else None, want_marginals=True)
+                                obs_cov=self.fx_covs_obs if obs else None, want_marginals=True, thin=f.get("thin", False))
             self._bufs["s"].update(Sig=s["Sig"], x=s["x"])
             self._q.update(mu=s["x"], Sig=s["Sig"])
         return self._q
