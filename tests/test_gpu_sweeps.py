@@ -326,3 +326,52 @@ def test_coarse_row_bodies_agree_with_lane_bodies(amd, rng, monkeypatch, B, T, d
     assert differs or d == 1 or fused_off, "the two routes produced bit-identical arrays: the row bodies did not run"   # 1 x 1 blocks: same operations
     Ld, Ls = np_btd.cholesky(diag, sub)
     assert_close(outs[0][0].cpu().numpy(), Ld)
+
+
+# B = 3, T = 257: R0 = 32 gives nine level-0 segments per chain, the last of one node, and one level above them; R0 = T is a single level
+BACKWARD_ROUTES = ["plain-rhs", "plain-norhs", "mom", "mom-sub", "s", "s-mom"]
+
+
+@pytest.mark.parametrize("levels", [1, 2])
+@pytest.mark.parametrize("route", BACKWARD_ROUTES)
+@pytest.mark.parametrize("d", [1, 3])
+def test_backward_sweep_combinations(amd, rng, d, route, levels):
+    """The level-0 forms of k_backward that the tests above and tests/test_gpu_sweep_stages.py, test_gpu_api.py and test_gpu_kf.py do not
+    reach, or reach only through a model.  Of the 20 legal values of <rhs, up, sub, moments, use-S, coarse> (launch_backward,
+    csrc/mfgm_api_sweeps.hip) those tests launch: the four coarse ones and <rhs, up, sub = 1> (test_dense_stages_equal_whole, which walks
+    every level with and without a right-hand side), <rhs, up = 0, sub = 1> (test_factor_and_selinv on its one-segment shapes),
+    <1, 1, 0> (test_full_size_properties), <0, 0, 0> (test_block_tri_diag), the moment array from L_{t+1,t} with Sub on two levels
+    (test_prior_parameter_gradients_and_learning), use-S with moments on several levels (test_fused_dense_sweeps_by_level) and
+    without (the predict calls of test_gpu_kf.py).  Here, with and without a level above: marginals without Sub (plain), the
+    moment array from L_{t+1,t} without and with Sub (mom), and the sweep that reads S for L_{t+1,t} without and with the moment array
+    (s).  Against the oracle of test_factor_and_selinv, at its tolerance."""
+    B, T = 3, 257
+    diag, sub = random_dominant_btd(rng, (B,), T, d)
+    r = rng.normal(size=(B, T, d))
+    plan = amd.Plan(B, T, d, R0=32 if levels == 2 else T)
+    assert plan.nlevels == levels
+    with_rhs = route != "plain-norhs"
+    Dp, Sp = plan.pack(amd.SYM, _dev(diag)), plan.pack(amd.FULL, _dev(sub))
+    f = plan.factor(Dp, Sp, plan.pack(amd.VEC, _dev(r)) if with_rhs else None, store_G=not route.startswith("s"))
+    plan.check_info()
+    if route.startswith("plain"):
+        s = plan.selinv(f["L"], f["G"], f["y"], want_sub=False)
+    elif route.startswith("mom"):
+        s = plan.selinv_mom(f["L"], f["G"], f["y"], want_sub=route == "mom-sub")
+    elif route == "s":
+        s = plan.selinv_s(f["L"], Sp, 1.0, f["y"])
+    else:
+        s = plan.selinv_mom(f["L"], None, f["y"], S=Sp, aS=1.0)
+    Ld, Ls = np_btd.cholesky(diag, sub)
+    Sd, Ss = np_btd.inverse_blocks(Ld, Ls)
+    assert_close(plan.unpack(amd.SYM, s["Sig"]).cpu().numpy(), Sd)
+    if with_rhs:
+        x = np_btd.solve(Ld, Ls, np_btd.solve(Ld, Ls, r), transpose_left=True)
+        assert_close(plan.unpack(amd.VEC, s["x"]).cpu().numpy(), x)
+    if s.get("Sub") is not None:
+        assert_close(plan.unpack(amd.FULL, s["Sub"], T - 1).cpu().numpy(), Ss)
+    if s.get("mom") is not None:
+        mom = plan.unpack_moments(s["mom"]).cpu().numpy()          # (mu, diag Sigma_tt, diag Sigma_{t+1,t}); the last has T - 1 nodes
+        assert_close(mom[..., :d], x)
+        assert_close(mom[..., d:2 * d], np.diagonal(Sd, axis1=-2, axis2=-1))
+        assert_close(mom[:, :T - 1, 2 * d:], np.diagonal(Ss, axis1=-2, axis2=-1))

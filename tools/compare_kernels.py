@@ -1,7 +1,11 @@
-"""Kernel-by-kernel comparison of the gfx950 code objects of two `hipcc --cuda-device-only -c` objects of one translation unit: the
-set of kernel names, each kernel's code bytes (.text) and its 64-byte descriptor (.rodata).  For a host-only change of a unit both
-must be equal; kernels present on one side only are listed.
-usage: python tools/compare_kernels.py old.o new.o [--arch gfx950] [--llvm /opt/rocm/lib/llvm/bin]"""
+"""Kernel-by-kernel comparison of the gfx950 code of two builds: the set of kernel names, each kernel's code bytes (.text) and its
+64-byte descriptor (.rodata).  Each side is one or more objects -- `hipcc -c` objects as the Makefile builds them (the code object is
+taken out of their .hip_fatbin section) or `hipcc --cuda-device-only -c` ones -- and the comparison is over the union of a side by
+kernel name, so a kernel that moved from one translation unit to another is not a difference.  For a host-only change all must be
+equal; kernels present on one side only are listed.  A kernel that several units of a side carry (a small one from a shared header)
+is compared as the set of its distinct copies.
+usage: python tools/compare_kernels.py old.o new.o
+       python tools/compare_kernels.py --old old/*.o --new new/*.o        [--arch gfx950] [--llvm /opt/rocm/lib/llvm/bin]"""
 import argparse
 import os
 import re
@@ -10,14 +14,22 @@ import tempfile
 
 
 def code_object(obj, arch, llvm, tmp):
-    """The unbundled ELF of `obj` (or `obj` itself when it already is one)."""
+    """The gfx950 ELF of `obj`: `obj` itself when it is one, else unbundled from it or from the .hip_fatbin section of a host object."""
+    run = lambda *cmd: subprocess.run(cmd, check=True, capture_output=True)
+    out = os.path.join(tmp, f"{len(os.listdir(tmp))}_{os.path.basename(obj)}")
     with open(obj, "rb") as f:
-        if f.read(4) == b"\x7fELF":
+        head = f.read(20)
+    if head[:4] == b"\x7fELF":
+        if head[18:20] == b"\xe0\x00":           # e_machine = EM_AMDGPU
             return obj
-    out = os.path.join(tmp, os.path.basename(obj) + ".elf")
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--targets=hip-amdgcn-amd-amdhsa--{arch}",
-                    f"--input={obj}", f"--output={out}"], check=True)
-    return out
+        sections = subprocess.run([os.path.join(llvm, "llvm-readelf"), "-S", "-W", obj], capture_output=True, text=True, check=True).stdout
+        if ".hip_fatbin" not in sections:
+            return None                          # a unit without device code
+        run(os.path.join(llvm, "llvm-objcopy"), "--dump-section", f".hip_fatbin={out}.fatbin", obj)
+        obj = out + ".fatbin"
+    run(os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", f"--targets=hip-amdgcn-amd-amdhsa--{arch}",
+        f"--input={obj}", f"--output={out}.elf")
+    return out + ".elf"
 
 
 def kernels(elf, llvm):
@@ -44,15 +56,32 @@ def kernels(elf, llvm):
     return {n: (func[n], desc[n]) for n in desc if n in func}
 
 
+def side(objs, arch, llvm, tmp, label):
+    """{kernel name: the set of its distinct (code, descriptor) copies} over `objs`, with the per-object counts printed."""
+    union = {}
+    for o in objs:
+        elf = code_object(o, arch, llvm, tmp)
+        ks = kernels(elf, llvm) if elf else {}
+        print(f"{label} {o}: {len(ks)} kernels")
+        for n, k in ks.items():
+            union.setdefault(n, set()).add(k)
+    return union
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("old")
-    ap.add_argument("new")
+    ap.add_argument("pair", nargs="*", help="old.o new.o")
+    ap.add_argument("--old", nargs="+", default=[])
+    ap.add_argument("--new", nargs="+", default=[])
     ap.add_argument("--arch", default="gfx950")
     ap.add_argument("--llvm", default="/opt/rocm/lib/llvm/bin")
     a = ap.parse_args()
+    if a.pair and (a.old or a.new or len(a.pair) != 2) or not a.pair and not (a.old and a.new):
+        ap.error("give either old.o new.o, or --old ... --new ...")
+    if a.pair:
+        a.old, a.new = a.pair[:1], a.pair[1:]
     with tempfile.TemporaryDirectory() as tmp:
-        old, new = (kernels(code_object(o, a.arch, a.llvm, tmp), a.llvm) for o in (a.old, a.new))
+        old, new = (side(objs, a.arch, a.llvm, tmp, label) for objs, label in ((a.old, "old"), (a.new, "new")))
     demangle = lambda n: subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip().split("(")[0]
     for n in sorted(old.keys() - new.keys()):
         print("only in old:", demangle(n))
@@ -60,10 +89,13 @@ def main():
         print("only in new:", demangle(n))
     differ = 0
     for n in sorted(old.keys() & new.keys()):
-        code, kd = old[n][0] == new[n][0], old[n][1] == new[n][1]
-        if not (code and kd):
-            differ += 1
-            print("differs:", demangle(n), "" if code else f"code ({len(old[n][0])} -> {len(new[n][0])} bytes)", "" if kd else "descriptor")
+        if old[n] == new[n]:
+            if len(old[n]) > 1:
+                print(f"equal on both sides, in {len(old[n])} distinct copies (units built with different flags):", demangle(n))
+            continue
+        differ += 1
+        (oc, ok), (nc, nk) = min(old[n] - new[n] or old[n]), min(new[n] - old[n] or new[n])
+        print("differs:", demangle(n), "" if oc == nc else f"code ({len(oc)} -> {len(nc)} bytes)", "" if ok == nk else "descriptor")
     print(f"kernels: {len(old)} old, {len(new)} new, {len(old.keys() & new.keys())} in both, {differ} of those differ")
 
 

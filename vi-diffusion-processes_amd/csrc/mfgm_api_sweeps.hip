@@ -12,71 +12,41 @@ namespace {
 
 template <int D>
 int launch_reduce(const SweepArgs& a, bool has_rhs, bool has_corr, hipStream_t st) {
-    dim3 grid(a.lv.Lpad / 64), block(64);
-    if (has_rhs) {
-        if (has_corr) hipLaunchKernelGGL((k_reduce<D, true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_reduce<D, true, false>), grid, block, 0, st, a);
-    } else {
-        if (has_corr) hipLaunchKernelGGL((k_reduce<D, false, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_reduce<D, false, false>), grid, block, 0, st, a);
-    }
+    pick([&](auto rhs, auto corr) { hipLaunchKernelGGL((k_reduce<D, rhs, corr>), dim3(a.lv.Lpad / 64), dim3(64), 0, st, a); },
+         has_rhs, has_corr);
     MFGM_CHECK_LAUNCH();
     return 0;
 }
 
 template <int D>
 int launch_forward(const SweepArgs& a, bool has_rhs, bool has_corr, bool has_up, hipStream_t st) {
-    dim3 grid(a.lv.Lpad / 64), block(64);
-#define FW(R_, C_, U_) hipLaunchKernelGGL((k_forward<D, R_, C_, U_>), grid, block, 0, st, a)
-    if (has_rhs) {
-        if (has_corr) { if (has_up) FW(true, true, true); else FW(true, true, false); }
-        else { if (has_up) FW(true, false, true); else FW(true, false, false); }
-    } else {
-        if (has_corr) { if (has_up) FW(false, true, true); else FW(false, true, false); }
-        else { if (has_up) FW(false, false, true); else FW(false, false, false); }
-    }
-#undef FW
+    pick([&](auto rhs, auto corr, auto up) { hipLaunchKernelGGL((k_forward<D, rhs, corr, up>), dim3(a.lv.Lpad / 64), dim3(64), 0, st, a); },
+         has_rhs, has_corr, has_up);
     MFGM_CHECK_LAUNCH();
     return 0;
 }
 
+// k_backward exists for 20 of the 64 values of its six switches <rhs, up, sub, moments, use-S, coarse>:
+//   a level above the finest one (coarse)            rhs x up          workspace arrays (coarse_off), marginals only: no Sub, no moments
+//   level 0 rebuilt from the input S (use-S)         up x moments      the forward pass stored no L_{t+1,t}; means wanted, no Sub
+//   level 0 with the moment array                    up x sub          the moments need the means: rhs is guaranteed by the entry point
+//   level 0, marginals (and Sub)                     rhs x up x sub
+// Anything else is refused (1) before the launch; the `if constexpr` keeps it from being instantiated.
 template <int D>
 int launch_backward(const SweepArgs& a, bool has_rhs, bool has_up, bool want_sub, hipStream_t st, bool coarse = false) {
-    dim3 grid(a.lv.Lpad / 64), block(64);
-    const bool mom = (a.momg != nullptr);
-    if (coarse) {
-        // a level above the finest one: workspace arrays (coarse_off), marginals only
-        if (want_sub || mom || a.Gg == nullptr) return 1;
-#define BWC(R_, U_) hipLaunchKernelGGL((k_backward<D, R_, U_, false, false, false, true>), grid, block, 0, st, a)
-        if (has_rhs) { if (has_up) BWC(true, true); else BWC(true, false); }
-        else { if (has_up) BWC(false, true); else BWC(false, false); }
-#undef BWC
-        MFGM_CHECK_LAUNCH();
-        return 0;
-    }
-#define BW(R_, U_, S_, M_) hipLaunchKernelGGL((k_backward<D, R_, U_, S_, M_>), grid, block, 0, st, a)
-    if (a.Gg == nullptr && a.Sg != nullptr) {
-        // level 0 rebuilt from the input sub-diagonal blocks (the forward pass stored no L_{t+1,t}); means wanted, no Sub
-        if (want_sub || !has_rhs) return 1;
-        if (mom) {
-            if (has_up) hipLaunchKernelGGL((k_backward<D, true, true, false, true, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_backward<D, true, false, false, true, true>), grid, block, 0, st, a);
-        } else {
-            if (has_up) hipLaunchKernelGGL((k_backward<D, true, true, false, false, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_backward<D, true, false, false, false, true>), grid, block, 0, st, a);
+    const bool mom = (a.momg != nullptr), use_s = !coarse && a.Gg == nullptr && a.Sg != nullptr;
+    if (coarse && (want_sub || mom || a.Gg == nullptr)) return 1;
+    if (use_s && (want_sub || !has_rhs)) return 1;
+    const dim3 grid(a.lv.Lpad / 64), block(64);
+    pick([&](auto rhs, auto up, auto sub, auto m) {
+        if (coarse) {
+            if constexpr (!sub && !m) hipLaunchKernelGGL((k_backward<D, rhs, up, false, false, false, true>), grid, block, 0, st, a);
+        } else if (use_s) {
+            if constexpr (rhs && !sub) hipLaunchKernelGGL((k_backward<D, true, up, false, m, true>), grid, block, 0, st, a);
+        } else if constexpr (rhs || !m) {
+            hipLaunchKernelGGL((k_backward<D, rhs, up, sub, m>), grid, block, 0, st, a);
         }
-    } else if (mom) {
-        // the moment array needs the means: has_rhs is guaranteed by the entry point
-        if (has_up) { if (want_sub) BW(true, true, true, true); else BW(true, true, false, true); }
-        else { if (want_sub) BW(true, false, true, true); else BW(true, false, false, true); }
-    } else if (has_rhs) {
-        if (has_up) { if (want_sub) BW(true, true, true, false); else BW(true, true, false, false); }
-        else { if (want_sub) BW(true, false, true, false); else BW(true, false, false, false); }
-    } else {
-        if (has_up) { if (want_sub) BW(false, true, true, false); else BW(false, true, false, false); }
-        else { if (want_sub) BW(false, false, true, false); else BW(false, false, false, false); }
-    }
-#undef BW
+    }, has_rhs || mom, has_up, want_sub, mom);
     MFGM_CHECK_LAUNCH();
     return 0;
 }
@@ -130,8 +100,8 @@ int coarse_up(const Plan& P, double* ws, int* info, bool has_rhs, hipStream_t st
     for (int l = 1; l < K && l < lf; ++l)
         if (int rc = reduce_level<D>(P, l, ws, info, has_rhs, st)) return rc;
     if (lf <= K) {
-        if (has_rhs) hipLaunchKernelGGL((k_coarse_factor<D, true>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p());
-        else hipLaunchKernelGGL((k_coarse_factor<D, false>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p());
+        pick([&](auto rhs) { hipLaunchKernelGGL((k_coarse_factor<D, rhs>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, info, coarse_rows_p()); },
+             has_rhs);
         MFGM_CHECK_LAUNCH();
     }
     for (int l = std::min(K, lf - 1); l >= 1; --l)
@@ -143,8 +113,8 @@ template <int D>
 int coarse_down(const Plan& P, double* ws, bool has_rhs, hipStream_t st) {
     const int K = P.nlevels - 1, lf = coarse_fuse_from(P);
     if (lf <= K) {
-        if (has_rhs) hipLaunchKernelGGL((k_coarse_backward<D, true>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p());
-        else hipLaunchKernelGGL((k_coarse_backward<D, false>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p());
+        pick([&](auto rhs) { hipLaunchKernelGGL((k_coarse_backward<D, rhs>), dim3(P.B), dim3(kCoarseBlock), 0, st, P, lf, ws, coarse_rows_p()); },
+             has_rhs);
         MFGM_CHECK_LAUNCH();
     }
     for (int l = std::min(K, lf - 1); l >= 1; --l)
@@ -167,8 +137,7 @@ int coarse_up_pair(const Plan& P, double* ws, size_t shift, int* info, hipStream
     }
     for (int l = std::min(K, lf - 1); l >= 1; --l) {
         const SweepArgs a = coarse_level_args(P, l, ws, info), b = coarse_level_args(P, l, ws + shift, info);
-        if (l < K) hipLaunchKernelGGL((k_forward_pair<D, true>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b);
-        else hipLaunchKernelGGL((k_forward_pair<D, false>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b);
+        pick([&](auto up) { hipLaunchKernelGGL((k_forward_pair<D, up>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b); }, l < K);
         MFGM_CHECK_LAUNCH();
     }
     return 0;
@@ -182,8 +151,7 @@ int coarse_down_pair(const Plan& P, double* ws, size_t shift, hipStream_t st) {
     }
     for (int l = std::min(K, lf - 1); l >= 1; --l) {
         const SweepArgs a = coarse_level_args(P, l, ws, nullptr), b = coarse_level_args(P, l, ws + shift, nullptr);
-        if (l < K) hipLaunchKernelGGL((k_backward_pair<D, true>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b);
-        else hipLaunchKernelGGL((k_backward_pair<D, false>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b);
+        pick([&](auto up) { hipLaunchKernelGGL((k_backward_pair<D, up>), dim3(2 * (a.lv.Lpad / 64)), dim3(64), 0, st, a, b); }, l < K);
         MFGM_CHECK_LAUNCH();
     }
     return 0;
@@ -214,14 +182,11 @@ int factor_impl(const Plan& P, const double* Dg, const double* Sg, const double*
     // single-kernel profiling calls above the finest level: that level's reduce or forward alone, no fusing
     if (only_stage == 0 && only_level > 0) return reduce_level<D>(P, only_level, ws, info, has_rhs, st);
     if (only_stage == 1 && only_level > 0) return forward_level<D>(P, only_level, ws, info, has_rhs, st);
-    SweepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.lv = P.lv[0];
+    SweepArgs a = level0_args(P, ws);
     a.info = info;
     a.Dg = Dg; a.Sg = Sg; a.rg = rg; a.aD = aD; a.aS = aS; a.aR = aR;
     a.Lg = Lg; a.Gg = Gg; a.yg = yg;
     a.part = (logdet || quad || partials_only) ? ws + P.off_part[0] : nullptr;
-    if (K > 0) bind_up(P, 0, ws, a);
     if (K > 0 && only_stage <= 0)
         if (int rc = launch_reduce<D>(a, has_rhs, false, st)) return rc;
     if (only_stage < 0)
@@ -244,13 +209,10 @@ int selinv_impl(const Plan& P, const double* Lg, const double* Gg, const double*
     if (only_level > 0) return backward_level<D>(P, only_level, ws, has_rhs, st);      // profiling: that level alone, no fusing
     if (only_level < 0)
         if (int rc = coarse_down<D>(P, ws, has_rhs, st)) return rc;
-    SweepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.lv = P.lv[0];
+    SweepArgs a = level0_args(P, ws);
     a.Lg = const_cast<double*>(Lg); a.Gg = const_cast<double*>(Gg); a.yg = const_cast<double*>(yg);
     a.Sigg = Sig; a.Subg = Sub; a.mug = x; a.momg = mom;
     a.Sg = Sg; a.aS = aS;          // non-null Sg: level 0 reads S instead of L_{t+1,t} (see k_backward, USE_S)
-    if (K > 0) bind_up(P, 0, ws, a);
     return launch_backward<D>(a, has_rhs, K > 0, Sub != nullptr, st);
 }
 
@@ -261,11 +223,8 @@ int selinv_girsanov_impl(const Plan& P, const double* Lg, const double* Sg, doub
     if (only_level > 0) return backward_level<D>(P, only_level, ws, true, st);
     if (only_level < 0)
         if (int rc = coarse_down<D>(P, ws, true, st)) return rc;
-    SweepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.lv = P.lv[0];
+    SweepArgs a = level0_args(P, ws);
     a.Lg = const_cast<double*>(Lg); a.yg = const_cast<double*>(yg); a.Sg = Sg; a.aS = aS;
-    bind_up(P, 0, ws, a);
     GirsanovArgs ga = g;
     ga.fix = ws + P.off_part[0];
     dim3 grid(a.lv.Lpad / 64), block(64);
@@ -282,13 +241,10 @@ int selinv_kl_impl(const Plan& P, const double* Lg, const double* Sg, double aS,
     if (only_level > 0) return backward_level<D>(P, only_level, ws, true, st);
     if (only_level < 0)
         if (int rc = coarse_down<D>(P, ws, true, st)) return rc;
-    SweepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.lv = P.lv[0];
+    SweepArgs a = level0_args(P, ws);
     a.Lg = const_cast<double*>(Lg); a.yg = const_cast<double*>(yg); a.Sg = Sg; a.aS = aS;
     a.Sigg = Sig; a.mug = x;
     a.part = ws + P.off_part[0];
-    bind_up(P, 0, ws, a);
     hipLaunchKernelGGL((k_backward_kl<D>), dim3(a.lv.Lpad / 64), dim3(64), 0, st, a, pr);
     MFGM_CHECK_LAUNCH();
     return sum_level0_partials(P, ws, 0, kl, nullptr, st);
@@ -322,19 +278,22 @@ Plan with_l1_region(const Plan& P, int r) {
     return Q;
 }
 
+// level 0 of a factorisation of a cq state: natural parameters -> precision on load
+SweepArgs cq_factor_args(const Plan& P, double* ws, double* Lg, double* yg, bool want_sums, int* info) {
+    SweepArgs a = level0_args(P, ws);
+    a.info = info;
+    a.aD = -2.0; a.aS = -1.0; a.aR = 1.0;
+    a.Lg = Lg; a.yg = yg;
+    a.part = want_sums ? ws + P.off_part[0] : nullptr;
+    return a;
+}
+
 template <int D>
 int cq_factor_impl(const Plan& P0, const CqArgs& q, double* Lg, double* yg, double* logdet, double* quad, double* ws, int* info,
                    hipStream_t st, int only_stage = -1, const CqPipe* pipe = nullptr) {
     const int region = (pipe && pipe->use_ahead) ? pipe->owner->ahead_region : 0;
     const Plan P = with_l1_region(P0, region);
-    SweepArgs a0;
-    memset(&a0, 0, sizeof(a0));
-    a0.lv = P.lv[0];
-    a0.info = info;
-    a0.aD = -2.0; a0.aS = -1.0; a0.aR = 1.0;          // natural parameters -> precision
-    a0.Lg = Lg; a0.yg = yg;
-    a0.part = (logdet || quad) ? ws + P.off_part[0] : nullptr;
-    bind_up(P, 0, ws, a0);
+    const SweepArgs a0 = cq_factor_args(P, ws, Lg, yg, logdet || quad, info);
     dim3 grid(a0.lv.Lpad / 64), block(64);
     if (pipe && pipe->use_ahead) {
         // the separator system of this state was made ahead in the region bound above; when that happened on a side stream: wait for it
@@ -377,14 +336,10 @@ int cq_factor_impl(const Plan& P0, const CqArgs& q, double* Lg, double* yg, doub
                 CqArgs qf = q;
                 qf.site_lin2 = next->site_lin; qf.site_sym2 = next->site_sym;
                 qf.pre_Dhat = an.uDhat; qf.pre_Rsub = an.uRsub; qf.pre_S = an.uS; qf.pre_rhat = an.urhat; qf.pre_rho = an.urho;
-                if (a0.lv.nt >= 1) hipLaunchKernelGGL((k_forward_reduce_cq<D, 1>), grid, dim3(128), 0, st, a0, qf);
-                else hipLaunchKernelGGL((k_forward_reduce_cq<D>), grid, dim3(128), 0, st, a0, qf);
+                pick([&](auto nt) { hipLaunchKernelGGL((k_forward_reduce_cq<D, nt ? 1 : 0>), grid, dim3(128), 0, st, a0, qf); }, a0.lv.nt >= 1);
             }
         }
-        if (!rides) {
-            if (a0.lv.nt >= 2) hipLaunchKernelGGL((k_forward_cq<D, 2>), grid, block, 0, st, a0, q);
-            else hipLaunchKernelGGL((k_forward_cq<D>), grid, block, 0, st, a0, q);
-        }
+        if (!rides) pick([&](auto nt) { hipLaunchKernelGGL((k_forward_cq<D, nt ? 2 : 0>), grid, block, 0, st, a0, q); }, a0.lv.nt >= 2);
         MFGM_CHECK_LAUNCH();
         if (next && !side && !rides) {
             hipLaunchKernelGGL((k_reduce_cq_lean<D>), grid, block, 0, st, an, *next);
@@ -401,8 +356,7 @@ int cq_factor_impl(const Plan& P0, const CqArgs& q, double* Lg, double* yg, doub
 // the separator marginals of their factorisation in place.  Every body is the one the single route runs: same numbers.
 template <int D>
 int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double* Lg, double* yg, double* logdet, double* quad, double* L2,
-                        double* y2, double* ws, int* info, hipStream_t st, int only_stage = -1, double* park = nullptr, int stride = 0,
-                        bool thin = false) {
+                        double* y2, double* ws, int* info, hipStream_t st, int only_stage, double* park, int stride, bool thin) {
     // thin (mfgm_cq_factor_pair_thin, d <= 6): (Lg, yg) receives the records of the kept nodes only; (L2, y2) is full either way
     // park (mfgm_cq_factor_pair_heads): the two level-0 reduces share the elimination of everything but the observed nodes
     // only_stage (profiling): 0 the two level-0 reduces, 1 the level-0 forward pair, 2 the joint up phase of the levels above, 3 their
@@ -410,16 +364,9 @@ int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double
     const auto on = [&](int s) { return only_stage < 0 || only_stage == s; };
     const size_t sh = P.off_pair - P.off_Dhat[1];
     double* ws2 = ws + sh;                            // (only the offsets of levels >= 1 are ever added to it)
-    SweepArgs a0;
-    memset(&a0, 0, sizeof(a0));
-    a0.lv = P.lv[0];
-    a0.info = info;
-    a0.aD = -2.0; a0.aS = -1.0; a0.aR = 1.0;
-    a0.Lg = Lg; a0.yg = yg;
-    a0.part = (logdet || quad) ? ws + P.off_part[0] : nullptr;
+    const SweepArgs a0 = cq_factor_args(P, ws, Lg, yg, logdet || quad, info);
     SweepArgs a1 = a0;
     a1.Lg = L2; a1.yg = y2; a1.part = nullptr;
-    bind_up(P, 0, ws, a0);
     bind_up(P, 0, ws2, a1);
     dim3 grid(a0.lv.Lpad / 64), block(64);
     if (on(0) && park) {
@@ -438,23 +385,17 @@ int cq_factor_pair_impl(const Plan& P, const CqArgs& q, const CqArgs& q2, double
     if (!on(1)) {
         // (profiling call for another stage)
     } else if constexpr (D <= 6) {
-        const dim3 pair(128);
-        const bool nt1 = a0.lv.nt >= 1;
-        if (thin) {
-            if (nt1) hipLaunchKernelGGL((k_forward_pair_thin_cq<D, 1>), grid, pair, 0, st, a0, q, a1, q2);
-            else hipLaunchKernelGGL((k_forward_pair_thin_cq<D>), grid, pair, 0, st, a0, q, a1, q2);
-        } else if (nt1) hipLaunchKernelGGL((k_forward_pair_cq<D, 1>), grid, pair, 0, st, a0, q, a1, q2);
-        else hipLaunchKernelGGL((k_forward_pair_cq<D>), grid, pair, 0, st, a0, q, a1, q2);
+        pick([&](auto th, auto nt) {
+            if constexpr (th) hipLaunchKernelGGL((k_forward_pair_thin_cq<D, nt ? 1 : 0>), grid, dim3(128), 0, st, a0, q, a1, q2);
+            else hipLaunchKernelGGL((k_forward_pair_cq<D, nt ? 1 : 0>), grid, dim3(128), 0, st, a0, q, a1, q2);
+        }, thin, a0.lv.nt >= 1);
         MFGM_CHECK_LAUNCH();
     } else {
         // d = 7, 8: the body does not fit 256 registers; one forward sweep after the other
-        if (a0.lv.nt >= 2) {
-            hipLaunchKernelGGL((k_forward_cq<D, 2>), grid, block, 0, st, a0, q);
-            hipLaunchKernelGGL((k_forward_cq<D, 2>), grid, block, 0, st, a1, q2);
-        } else {
-            hipLaunchKernelGGL((k_forward_cq<D>), grid, block, 0, st, a0, q);
-            hipLaunchKernelGGL((k_forward_cq<D>), grid, block, 0, st, a1, q2);
-        }
+        pick([&](auto nt) {
+            hipLaunchKernelGGL((k_forward_cq<D, nt ? 2 : 0>), grid, block, 0, st, a0, q);
+            hipLaunchKernelGGL((k_forward_cq<D, nt ? 2 : 0>), grid, block, 0, st, a1, q2);
+        }, a0.lv.nt >= 2);
         MFGM_CHECK_LAUNCH();
     }
     if (logdet || quad)
@@ -470,15 +411,11 @@ int cq_selinv_girsanov_impl(const Plan& P, const CqArgs& q, const double* Lg, co
     double* wsc = alt ? ws + (P.off_pair - P.off_Dhat[1]) : ws;
     if (only_level != 0)
         if (int rc = coarse_down<D>(P, wsc, true, st)) return rc;
-    SweepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.lv = P.lv[0];
+    SweepArgs a = level0_args(P, wsc);
     a.Lg = const_cast<double*>(Lg); a.yg = const_cast<double*>(yg); a.aS = -1.0;
-    bind_up(P, 0, wsc, a);
     double* fix = ws + P.off_part[0];
     dim3 grid(a.lv.Lpad / 64), block(64);
-    if (a.lv.nt >= 2) hipLaunchKernelGGL((k_backward_girsanov_cq<D, 2>), grid, block, 0, st, a, pr, q, fix);
-    else hipLaunchKernelGGL((k_backward_girsanov_cq<D>), grid, block, 0, st, a, pr, q, fix);
+    pick([&](auto nt) { hipLaunchKernelGGL((k_backward_girsanov_cq<D, nt ? 2 : 0>), grid, block, 0, st, a, pr, q, fix); }, a.lv.nt >= 2);
     MFGM_CHECK_LAUNCH();
     hipLaunchKernelGGL((k_girsanov_fixup_cq<D>), grid, block, 0, st, a.lv, q.dyn_out, (const double*)fix);
     MFGM_CHECK_LAUNCH();
@@ -492,23 +429,18 @@ int cq_selinv_kl_impl(const Plan& P, const CqArgs& q, const double* Lg, const do
     if (only_level != 0)
         if (int rc = coarse_down<D>(P, ws, true, st)) return rc;
     if (only_level > 0) return 0;                    // profiling: the levels above the finest one alone
-    SweepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.lv = P.lv[0];
+    SweepArgs a = level0_args(P, ws);
     a.Lg = const_cast<double*>(Lg); a.yg = const_cast<double*>(yg); a.aS = -1.0;
     a.Sigg = Sig; a.mug = x;
     a.part = ws + P.off_part[0];
-    bind_up(P, 0, ws, a);
+    // thin: (Lg, yg) holds the kept records only (mfgm_cq_factor_pair_thin); the forward step of the sweep that rebuilds the others
+    // takes the factorisation's scales.  (thin at D > 6 never gets here: refused above, and the lambda below has no kernel for it)
+    if (thin) { a.aD = -2.0; a.aR = 1.0; }
     const dim3 grid(a.lv.Lpad / 64), block(64);
-    if (thin) {
-        // (Lg, yg) holds the kept records only (mfgm_cq_factor_pair_thin): the sweep that rebuilds the others
-        if constexpr (D <= 6) {
-            a.aD = -2.0; a.aR = 1.0;                 // the forward step that rebuilds a record takes the factorisation's scales
-            if (a.lv.nt >= 2) hipLaunchKernelGGL((k_backward_kl_thin_cq<D, 2>), grid, block, 0, st, a, pr, q);
-            else hipLaunchKernelGGL((k_backward_kl_thin_cq<D>), grid, block, 0, st, a, pr, q);
-        }
-    } else if (a.lv.nt >= 2) hipLaunchKernelGGL((k_backward_kl_cq<D, 2>), grid, block, 0, st, a, pr, q);
-    else hipLaunchKernelGGL((k_backward_kl_cq<D>), grid, block, 0, st, a, pr, q);
+    pick([&](auto th, auto nt) {
+        if constexpr (!th) hipLaunchKernelGGL((k_backward_kl_cq<D, nt ? 2 : 0>), grid, block, 0, st, a, pr, q);
+        else if constexpr (D <= 6) hipLaunchKernelGGL((k_backward_kl_thin_cq<D, nt ? 2 : 0>), grid, block, 0, st, a, pr, q);
+    }, thin, a.lv.nt >= 2);
     MFGM_CHECK_LAUNCH();
     return sum_level0_partials(P, ws, 0, kl, nullptr, st);
 }
@@ -534,6 +466,25 @@ int mvn_ve_compact_impl(int B, int n_per, const double* mu, const double* cov, c
     return 0;
 }
 
+bool cq_ok(const mfgm_plan* plan, const mfgm_cq_state* q) {
+    if (!plan || !q || !q->dyn) return false;
+    const Plan& P = plan->p;
+    if (P.wide || P.nlevels < 2) return false;
+    if (q->slot && (!q->site_lin || !q->site_sym)) return false;
+    return true;
+}
+// the pair calls: one dyn (same array, same layout) with two sets of observation sites, two distinct sets of outputs
+bool cq_pair_ok(const mfgm_plan* plan, const mfgm_cq_state* q, const mfgm_cq_state* q_next, const double* L, const double* y,
+                const double* L2, const double* y2, const void* ws, const int* info) {
+    if (!cq_ok(plan, q) || !cq_ok(plan, q_next) || !L || !y || !L2 || !y2 || L2 == L || y2 == y || !ws || !info) return false;
+    return plan->p.off_pair != 0 && q_next->dyn == q->dyn && q_next->slot == q->slot && q_next->p0_off == q->p0_off &&
+           q_next->d_off == q->d_off && q_next->s_off == q->s_off;
+}
+// the heads forms park the shared elimination in `scratch` (the parked stores must not leave the array)
+bool cq_heads_ok(const mfgm_plan* plan, int stride, const double* scratch, size_t scratch_doubles) {
+    return scratch && stride >= 2 && plan->p.lv[0].R % stride == 0 && scratch_doubles >= mfgm_cq_heads_scratch_doubles(plan, stride);
+}
+
 // ---- Kalman filter with sites, time-invariant emission (mfgm_kf.h) ------------------------------------------------------------------
 template <int D, int O>
 int kf_assemble_impl(const Plan& P, const KfArgs& k, const double* Pd, const double* plin, double* Dg, double* rg, double* t1,
@@ -547,55 +498,6 @@ int kf_assemble_impl(const Plan& P, const KfArgs& k, const double* Pd, const dou
     }
     return 0;
 }
-// The four per-chain sums of the Kalman log-likelihood with sites and its assembly (kalman_filter.py:229-255) in two launches instead
-// of five: part = [log|L|, |y|^2, t1, ldR] x [Lpad] per-lane partials; stage 1: kElboSplit blocks per chain sum a slice of each
-// array (fixed order: deterministic), stage 2: one block adds those and forms
-//   ll_b = cst - 1/2 t1 + 1/2 |y|^2 - sumlogchol_b - log|L| + 1/2 ldR      (NaN when a pivot block was not positive definite).
-constexpr int kElboSplit = 64;
-static __global__ __launch_bounds__(256) void k_kf_elbo_stage1(const double* __restrict__ part, int P, int Lpad, double* __restrict__ scratch) {
-    __shared__ double sh[4][4];
-    const int g = blockIdx.x, b = blockIdx.y, B = gridDim.y;
-    const int slice = (P + kElboSplit - 1) / kElboSplit, lo = g * slice, hi = min(P, lo + slice);
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int p = lo + threadIdx.x; p < hi; p += blockDim.x) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] += part[(size_t)q * Lpad + (size_t)b * P + p];
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off, 64);
-        if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = s[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) scratch[((size_t)threadIdx.x * B + b) * kElboSplit + g] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
-}
-static __global__ __launch_bounds__(64) void k_kf_elbo_stage2(const double* __restrict__ scratch, int B, double cst, const double* __restrict__ sumlogchol,
-                                                             const int* __restrict__ info, double* __restrict__ terms, double* __restrict__ ll,
-                                                             double* __restrict__ total) {
-    // one wavefront; lane g holds the stage-1 partial g of each term, chains one after the other (B is small on this path)
-    const bool bad = info && *info != 0;
-    double tot = 0.0;
-    for (int b = 0; b < B; ++b) {
-        double s[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            s[q] = scratch[((size_t)q * B + b) * kElboSplit + threadIdx.x];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off, 64);
-            s[q] = __shfl(s[q], 0, 64);
-        }
-        double v = cst - 0.5 * s[2] + 0.5 * s[1] - sumlogchol[b] - s[0] + 0.5 * s[3];
-        if (bad) v = __builtin_nan("");
-        if (threadIdx.x == 0) {
-            if (terms) { terms[b] = s[2]; terms[B + b] = s[3]; terms[2 * B + b] = s[0]; terms[3 * B + b] = s[1]; }   // (t1, ldR, log|L|, |y|^2)
-            if (ll) ll[b] = v;
-        }
-        tot += v;
-    }
-    if (threadIdx.x == 0 && total) *total = tot;
-}
-
 template <int D, int O>
 int kf_elbo_impl(const Plan& P, const KfArgs& k, const double* Pd, const double* Ps, double* Dg, double* rg, double* L, double* y,
                  const double* sumlogchol, double cst, double* terms, double* ll, double* total, double* ws, int* info, hipStream_t st) {
@@ -621,20 +523,6 @@ int kf_loglik_impl(const Plan& P, const KfArgs& k, const double* Pd, const doubl
     return factor_impl<D>(P, Dg, Ps, rg, 1.0, 1.0, 1.0, L, nullptr, y, logdet, quad, ws, info, st);
 }
 template <int D, int O>
-int kf_predict_impl(const Plan& P, const KfArgs& k, const double* Pd, const double* Ps, const double* plin, double* Dg, double* rg,
-                    double* L, double* y, double* Sig, double* x, double* Fmu, double* Fvar, double* ws, int* info, hipStream_t st) {
-    int rc = kf_assemble_impl<D, O>(P, k, Pd, plin, Dg, rg, nullptr, nullptr, ws, st);
-    if (rc) return rc;
-    rc = factor_impl<D>(P, Dg, Ps, rg, 1.0, 1.0, 1.0, L, nullptr, y, nullptr, nullptr, ws, info, st);
-    if (rc) return rc;
-    rc = selinv_impl<D>(P, L, nullptr, y, Sig, nullptr, x, ws, st, -1, nullptr, Ps, 1.0);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_kf_project<D, O>), dim3(P.lv[0].Lpad / 64), dim3(64), 0, st, P.lv[0], P.T, k, (const double*)x,
-                       (const double*)Sig, Fmu, Fvar);
-    MFGM_CHECK_LAUNCH();
-    return 0;
-}
-template <int D, int O>
 int kf_predict_factored_impl(const Plan& P, const KfArgs& k, const double* Ps, const double* L, const double* y, double* Sig, double* x,
                              double* Fmu, double* Fvar, double* ws, hipStream_t st) {
     int rc = selinv_impl<D>(P, L, nullptr, y, Sig, nullptr, x, ws, st, -1, nullptr, Ps, 1.0);
@@ -643,6 +531,15 @@ int kf_predict_factored_impl(const Plan& P, const KfArgs& k, const double* Ps, c
                        (const double*)Sig, Fmu, Fvar);
     MFGM_CHECK_LAUNCH();
     return 0;
+}
+template <int D, int O>
+int kf_predict_impl(const Plan& P, const KfArgs& k, const double* Pd, const double* Ps, const double* plin, double* Dg, double* rg,
+                    double* L, double* y, double* Sig, double* x, double* Fmu, double* Fvar, double* ws, int* info, hipStream_t st) {
+    int rc = kf_assemble_impl<D, O>(P, k, Pd, plin, Dg, rg, nullptr, nullptr, ws, st);
+    if (rc) return rc;
+    rc = factor_impl<D>(P, Dg, Ps, rg, 1.0, 1.0, 1.0, L, nullptr, y, nullptr, nullptr, ws, info, st);
+    if (rc) return rc;
+    return kf_predict_factored_impl<D, O>(P, k, Ps, L, y, Sig, x, Fmu, Fvar, ws, st);
 }
 bool kf_args(const mfgm_plan* plan, const mfgm_kf_sites* sv, int mode, KfArgs& k) {
     if (!plan || !sv || !sv->nat1 || !sv->nat2 || plan->p.wide) return false;
@@ -656,25 +553,6 @@ bool kf_args(const mfgm_plan* plan, const mfgm_kf_sites* sv, int mode, KfArgs& k
 #define MFGM_DISPATCH_DO(d, o, CALL)                                      \
     if ((o) == 1) { constexpr int OO = 1; MFGM_DISPATCH_D(d, CALL); }     \
     else { constexpr int OO = 2; MFGM_DISPATCH_D(d, CALL); }
-
-bool cq_ok(const mfgm_plan* plan, const mfgm_cq_state* q) {
-    if (!plan || !q || !q->dyn) return false;
-    const Plan& P = plan->p;
-    if (P.wide || P.nlevels < 2) return false;
-    if (q->slot && (!q->site_lin || !q->site_sym)) return false;
-    return true;
-}
-// the pair calls: one dyn (same array, same layout) with two sets of observation sites, two distinct sets of outputs
-bool cq_pair_ok(const mfgm_plan* plan, const mfgm_cq_state* q, const mfgm_cq_state* q_next, const double* L, const double* y,
-                const double* L2, const double* y2, const void* ws, const int* info) {
-    if (!cq_ok(plan, q) || !cq_ok(plan, q_next) || !L || !y || !L2 || !y2 || L2 == L || y2 == y || !ws || !info) return false;
-    return plan->p.off_pair != 0 && q_next->dyn == q->dyn && q_next->slot == q->slot && q_next->p0_off == q->p0_off &&
-           q_next->d_off == q->d_off && q_next->s_off == q->s_off;
-}
-// the heads forms park the shared elimination in `scratch` (the parked stores must not leave the array)
-bool cq_heads_ok(const mfgm_plan* plan, int stride, const double* scratch, size_t scratch_doubles) {
-    return scratch && stride >= 2 && plan->p.lv[0].R % stride == 0 && scratch_doubles >= mfgm_cq_heads_scratch_doubles(plan, stride);
-}
 
 }  // namespace
 
@@ -758,20 +636,37 @@ int mfgm_cq_selinv_girsanov(const mfgm_plan* plan, int only_level, const mfgm_cq
     MFGM_DISPATCH_D(P.d, (cq_selinv_girsanov_impl<DD>(P, c, L, y, pr, (double*)ws, (hipStream_t)stream, only_level)));
 }
 
-int mfgm_cq_factor_pair(const mfgm_plan* plan, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y, double* logdet,
-                        double* quad, double* L2, double* y2, void* ws, int* info, void* stream) {
-    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info)) return 1;
+// The one front of the five exported pair calls: every argument rule of theirs is one of its lines.
+//   call                stage accepted      logdet, quad            heads (shared elimination parked in scratch)          thin
+//   _pair               (whole call)        as given                no                                                    no
+//   _pair_stage         0 ... 3             none (nulled)           no                                                    no
+//   _pair_heads         (whole call)        as given                yes: stride and scratch checked                       no
+//   _pair_heads_stage   0 ... 3             none (nulled)           yes: stride and scratch checked                       no
+//   _pair_thin          -1 ... 3            nulled when stage >= 0  stride == 0: no; else yes, stride and scratch checked yes
+// stage -1 is the whole call; the two *_stage calls refuse it themselves.  "stride and scratch checked" is cq_heads_ok: scratch given,
+// stride >= 2 and a divisor of the level-0 segment length, scratch_doubles >= mfgm_cq_heads_scratch_doubles(plan, stride).  Only the
+// thin call reads stride == 0 as "no heads"; for the heads calls it is an argument error.  thin at d > 6 is refused before any launch.
+static int cq_pair_front(const mfgm_plan* plan, int stage, bool heads, int stride, double* scratch, size_t scratch_doubles, bool thin,
+                         const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y, double* logdet, double* quad,
+                         double* L2, double* y2, void* ws, int* info, void* stream) {
+    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info) || stage < -1 || stage > 3 || (thin && plan->p.d > 6)) return 1;
+    if (heads && !cq_heads_ok(plan, stride, scratch, scratch_doubles)) return 1;
     const Plan& P = plan->p;
     const CqArgs c = cq_args(q), c2 = cq_args(q_next);
-    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, logdet, quad, L2, y2, (double*)ws, info, (hipStream_t)stream)));
+    if (stage >= 0) logdet = quad = nullptr;
+    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, logdet, quad, L2, y2, (double*)ws, info, (hipStream_t)stream, stage,
+                                                  heads ? scratch : nullptr, stride, thin)));
+}
+
+int mfgm_cq_factor_pair(const mfgm_plan* plan, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y, double* logdet,
+                        double* quad, double* L2, double* y2, void* ws, int* info, void* stream) {
+    return cq_pair_front(plan, -1, false, 0, nullptr, 0, false, q, q_next, L, y, logdet, quad, L2, y2, ws, info, stream);
 }
 
 int mfgm_cq_factor_pair_stage(const mfgm_plan* plan, int stage, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y,
                               double* L2, double* y2, void* ws, int* info, void* stream) {
-    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info) || stage < 0 || stage > 3) return 1;
-    const Plan& P = plan->p;
-    const CqArgs c = cq_args(q), c2 = cq_args(q_next);
-    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, nullptr, nullptr, L2, y2, (double*)ws, info, (hipStream_t)stream, stage)));
+    if (stage < 0) return 1;
+    return cq_pair_front(plan, stage, false, 0, nullptr, 0, false, q, q_next, L, y, nullptr, nullptr, L2, y2, ws, info, stream);
 }
 
 size_t mfgm_cq_heads_scratch_doubles(const mfgm_plan* plan, int stride) {
@@ -784,35 +679,20 @@ size_t mfgm_cq_heads_scratch_doubles(const mfgm_plan* plan, int stride) {
 int mfgm_cq_factor_pair_heads(const mfgm_plan* plan, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next, double* L, double* y,
                               double* logdet, double* quad, double* L2, double* y2, double* scratch, size_t scratch_doubles, void* ws, int* info,
                               void* stream) {
-    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info) || !cq_heads_ok(plan, stride, scratch, scratch_doubles)) return 1;
-    const Plan& P = plan->p;
-    const CqArgs c = cq_args(q), c2 = cq_args(q_next);
-    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, logdet, quad, L2, y2, (double*)ws, info, (hipStream_t)stream, -1, scratch,
-                                                  stride)));
+    return cq_pair_front(plan, -1, true, stride, scratch, scratch_doubles, false, q, q_next, L, y, logdet, quad, L2, y2, ws, info, stream);
 }
 
 int mfgm_cq_factor_pair_heads_stage(const mfgm_plan* plan, int stage, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next,
                                     double* L, double* y, double* L2, double* y2, double* scratch, size_t scratch_doubles, void* ws, int* info,
                                     void* stream) {
-    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info) || !cq_heads_ok(plan, stride, scratch, scratch_doubles) || stage < 0 ||
-        stage > 3)
-        return 1;
-    const Plan& P = plan->p;
-    const CqArgs c = cq_args(q), c2 = cq_args(q_next);
-    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, nullptr, nullptr, L2, y2, (double*)ws, info, (hipStream_t)stream, stage,
-                                                  scratch, stride)));
+    if (stage < 0) return 1;
+    return cq_pair_front(plan, stage, true, stride, scratch, scratch_doubles, false, q, q_next, L, y, nullptr, nullptr, L2, y2, ws, info, stream);
 }
 
 int mfgm_cq_factor_pair_thin(const mfgm_plan* plan, int stage, int stride, const mfgm_cq_state* q, const mfgm_cq_state* q_next,
                              double* L, double* y, double* logdet, double* quad, double* L2, double* y2, double* scratch, size_t scratch_doubles,
                              void* ws, int* info, void* stream) {
-    if (!cq_pair_ok(plan, q, q_next, L, y, L2, y2, ws, info) || plan->p.d > 6 || stage < -1 || stage > 3) return 1;
-    if (stride != 0 && !cq_heads_ok(plan, stride, scratch, scratch_doubles)) return 1;
-    const Plan& P = plan->p;
-    const CqArgs c = cq_args(q), c2 = cq_args(q_next);
-    if (stage >= 0) logdet = quad = nullptr;
-    MFGM_DISPATCH_D(P.d, (cq_factor_pair_impl<DD>(P, c, c2, L, y, logdet, quad, L2, y2, (double*)ws, info, (hipStream_t)stream, stage,
-                                                  stride ? scratch : nullptr, stride, true)));
+    return cq_pair_front(plan, stage, stride != 0, stride, scratch, scratch_doubles, true, q, q_next, L, y, logdet, quad, L2, y2, ws, info, stream);
 }
 
 int mfgm_cq_selinv_kl_thin(const mfgm_plan* plan, int only_level, const mfgm_cq_state* q, const double* L, const double* y,

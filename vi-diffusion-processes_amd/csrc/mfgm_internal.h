@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/mfgm.h"
 #include "mfgm_layout.h"
@@ -55,6 +56,17 @@ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
         case 4: { constexpr int DD = 4; return CALL; } \
         default: return 1;                   \
     }
+
+// One statement per launch decision: pick(f, on...) hands run-time choices to the generic lambda f as compile-time constants,
+// f(std::bool_constant<on>{}...).  f launches and returns nothing: MFGM_CHECK_LAUNCH() contains a `return` and goes after the call.
+// An `if constexpr` in f keeps a combination that is never launched from being instantiated.
+template <class F>
+void pick(F&& f) { f(); }
+template <class F, class... Bools>
+void pick(F&& f, bool on, Bools... rest) {
+    if (on) pick([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else pick([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
 
 // mfgm_api_wide.hip
 int wide_factor(const Plan& P, const double* Dg, const double* Sg, const double* rg, double aD, double aS, double aR,

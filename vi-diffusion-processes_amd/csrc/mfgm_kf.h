@@ -3,6 +3,7 @@
 //   k_kf_assemble : posterior precision blocks  D_t = K^{-1}_tt + H^T R_t^{-1} H  and the right-hand side, straight into the packed
 //                   layout, with the per-chain sums of the observation terms of the log-likelihood
 //   k_kf_project  : f-marginals  H mu_t,  diag(H Sigma_t H^T)  from the packed posterior marginals
+//   k_kf_elbo_stage1 / _stage2 : the four per-chain sums of the log-likelihood and its assembly (mfgm_kf_sites_elbo)
 // The reference does each of these with einsums over materialised [B, T, o, d] emission tensors plus a re-layout per access.
 #pragma once
 #include "mfgm_sweeps.h"
@@ -133,3 +134,59 @@ static __global__ __launch_bounds__(64) void k_kf_project(LevelDesc lv, int T, K
 }
 
 }  // namespace mfgm
+
+// The two reduction kernels of mfgm_kf_sites_elbo.  Unnamed namespace, not mfgm: the symbol names that tools/compare_kernels.py
+// matches the kernels of two builds by stay what earlier builds have.  This header is meant for mfgm_api_sweeps.hip alone: a
+// second unit that included it would get copies of its own of these two.
+namespace {
+
+// The four per-chain sums of the Kalman log-likelihood with sites and its assembly (kalman_filter.py:229-255) in two launches instead
+// of five: part = [log|L|, |y|^2, t1, ldR] x [Lpad] per-lane partials; stage 1: kElboSplit blocks per chain sum a slice of each
+// array (fixed order: deterministic), stage 2: one block adds those and forms
+//   ll_b = cst - 1/2 t1 + 1/2 |y|^2 - sumlogchol_b - log|L| + 1/2 ldR      (NaN when a pivot block was not positive definite).
+constexpr int kElboSplit = 64;
+static __global__ __launch_bounds__(256) void k_kf_elbo_stage1(const double* __restrict__ part, int P, int Lpad, double* __restrict__ scratch) {
+    __shared__ double sh[4][4];
+    const int g = blockIdx.x, b = blockIdx.y, B = gridDim.y;
+    const int slice = (P + kElboSplit - 1) / kElboSplit, lo = g * slice, hi = min(P, lo + slice);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int p = lo + threadIdx.x; p < hi; p += blockDim.x) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] += part[(size_t)q * Lpad + (size_t)b * P + p];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off, 64);
+        if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = s[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) scratch[((size_t)threadIdx.x * B + b) * kElboSplit + g] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
+}
+static __global__ __launch_bounds__(64) void k_kf_elbo_stage2(const double* __restrict__ scratch, int B, double cst, const double* __restrict__ sumlogchol,
+                                                             const int* __restrict__ info, double* __restrict__ terms, double* __restrict__ ll,
+                                                             double* __restrict__ total) {
+    // one wavefront; lane g holds the stage-1 partial g of each term, chains one after the other (B is small on this path)
+    const bool bad = info && *info != 0;
+    double tot = 0.0;
+    for (int b = 0; b < B; ++b) {
+        double s[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            s[q] = scratch[((size_t)q * B + b) * kElboSplit + threadIdx.x];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off, 64);
+            s[q] = __shfl(s[q], 0, 64);
+        }
+        double v = cst - 0.5 * s[2] + 0.5 * s[1] - sumlogchol[b] - s[0] + 0.5 * s[3];
+        if (bad) v = __builtin_nan("");
+        if (threadIdx.x == 0) {
+            if (terms) { terms[b] = s[2]; terms[B + b] = s[3]; terms[2 * B + b] = s[0]; terms[3 * B + b] = s[1]; }   // (t1, ldR, log|L|, |y|^2)
+            if (ll) ll[b] = v;
+        }
+        tot += v;
+    }
+    if (threadIdx.x == 0 && total) *total = tot;
+}
+
+}  // namespace

@@ -650,6 +650,13 @@ MFGM_HD SweepArgs coarse_level_args(const Plan& P, int l, double* ws, int* info)
     if (l < P.nlevels - 1) bind_up(P, l, ws, a);
     return a;
 }
+// The zeroed argument block of level 0, bound to the level above (in `ws`) when the plan has one: a driver sets only what is its own.
+inline SweepArgs level0_args(const Plan& P, double* ws) {
+    SweepArgs a = {};
+    a.lv = P.lv[0];
+    if (P.nlevels > 1) bind_up(P, 0, ws, a);
+    return a;
+}
 
 // ---- per-chain sum of the per-lane partials ---------------------------------------------------------
 // part: [2*Lpad]; out_logdet[b] = sum_p part[b*P+p]; out_quad[b] likewise.  One wave per chain.

@@ -93,6 +93,11 @@ class Plan:
         n = self.lib.mfgm_packed_doubles(self.h, kind)
         return torch.zeros(n, dtype=torch.float64, device=self.device)
 
+    def _held(self, out, key, kind):
+        """The array the buffer dict `out` already holds under `key`, else a fresh one of this kind (`out` itself is not touched)."""
+        held = out.get(key)
+        return self.empty(kind) if held is None else held
+
     def pack(self, kind, natural, out=None):
         """natural: [B, n_nodes, ...] contiguous fp64 device tensor; n_nodes = T or T-1."""
         natural = natural.contiguous()
@@ -122,13 +127,9 @@ class Plan:
         inverse form (mfgm_packed_factor_form, form 1), whose arrays are not Cholesky blocks."""
         out = {} if out is None else out
         form = 1 if (moments_only and self.wide and store_G and os.environ.get("MFGM_INVERSE_FORM", "1") != "0") else 0
-        L = out.get("L") if out.get("L") is not None else self.empty(TRI)
-        G = None
-        if store_G:
-            G = out.get("G") if out.get("G") is not None else self.empty(FULL)
-        y = None
-        if r is not None:
-            y = out.get("y") if out.get("y") is not None else self.empty(VEC)
+        L = self._held(out, "L", TRI)
+        G = self._held(out, "G", FULL) if store_G else None
+        y = self._held(out, "y", VEC) if r is not None else None
         self.epoch += 1
         out["thin"] = False      # (a buffer dict says whether the factor it holds is a thinned one: cq_factor_pair)
         logdet = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
@@ -143,9 +144,9 @@ class Plan:
         chain): the posterior naturals  prior + overlap-added sites  are formed by the level-0 passes while loading.
         packed: nat2 is the quadrant-packed tensor [M + 1, d (d + 1) + d^2] (mfgm_sparse_factor_q)."""
         out = {} if out is None else out
-        L = out.get("L") if out.get("L") is not None else self.empty(TRI)
-        G = out.get("G") if out.get("G") is not None else self.empty(FULL)
-        y = out.get("y") if out.get("y") is not None else self.empty(VEC)
+        L = self._held(out, "L", TRI)
+        G = self._held(out, "G", FULL)
+        y = self._held(out, "y", VEC)
         self.epoch += 1
         out["thin"] = False
         logdet = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
@@ -161,13 +162,9 @@ class Plan:
     def selinv(self, L, G, y=None, want_sub=True, out=None, form=0):
         """Selected inverse (+ backward substitution).  Returns dict(Sig, Sub, x).  `form`: the form of the factor arrays (`factor`)."""
         out = {} if out is None else out
-        Sig = out.get("Sig") if out.get("Sig") is not None else self.empty(SYM)
-        Sub = None
-        if want_sub:
-            Sub = out.get("Sub") if out.get("Sub") is not None else self.empty(FULL)
-        x = None
-        if y is not None:
-            x = out.get("x") if out.get("x") is not None else self.empty(VEC)
+        Sig = self._held(out, "Sig", SYM)
+        Sub = self._held(out, "Sub", FULL) if want_sub else None
+        x = self._held(out, "x", VEC) if y is not None else None
         _lib.check(self.lib.mfgm_packed_selinv_form(self.h, int(form), _ptr(L), _ptr(G), _ptr(y), _ptr(Sig), _ptr(Sub), _ptr(x),
                                                     _ptr(self.ws), _stream()), "mfgm_packed_selinv_form")
         return dict(Sig=Sig, Sub=Sub, x=x)
@@ -291,11 +288,9 @@ class Plan:
     def ssm_to_naturals(self, A, off, chol, precision=False, want_logdet=False, out=None):
         """Packed SSM parameters -> naturals (or precision blocks).  Returns dict(lin, diag, sub, sumlogchol)."""
         out = {} if out is None else out
-        lin = None
-        if off is not None:
-            lin = out.get("lin") if out.get("lin") is not None else self.empty(VEC)
-        diag = out.get("diag") if out.get("diag") is not None else self.empty(SYM)
-        sub = out.get("sub") if out.get("sub") is not None else self.empty(FULL)
+        lin = self._held(out, "lin", VEC) if off is not None else None
+        diag = self._held(out, "diag", SYM)
+        sub = self._held(out, "sub", FULL)
         slc = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
         cD, cS = (1.0, -1.0) if precision else (-0.5, 1.0)
         _lib.check(self.lib.mfgm_packed_ssm_to_naturals(self.h, _ptr(A), _ptr(off), _ptr(chol), cD, cS, _ptr(lin),
@@ -392,11 +387,9 @@ class Plan:
         """Selected inverse that also writes the moment array (mu, diag Sigma, diag Sigma_sub).  Returns dict(Sig, Sub, x, mom).
         With G = None the factorisation was made with store_G=False and (S, aS) are its sub-diagonal input and scale."""
         out = {} if out is None else out
-        Sig = out.get("Sig") if out.get("Sig") is not None else self.empty(SYM)
-        Sub = None
-        if want_sub:
-            Sub = out.get("Sub") if out.get("Sub") is not None else self.empty(FULL)
-        x = out.get("x") if out.get("x") is not None else self.empty(VEC)
+        Sig = self._held(out, "Sig", SYM)
+        Sub = self._held(out, "Sub", FULL) if want_sub else None
+        x = self._held(out, "x", VEC)
         mom = out.get("mom")
         if mom is None:
             mom = torch.empty(3 * x.numel(), dtype=torch.float64, device=self.device)
@@ -427,8 +420,8 @@ class Plan:
     def selinv_s(self, L, S, aS, y, out=None):
         """Selected inverse of a store_G=False factorisation: dict(Sig, x) (marginals only; (S, aS) as given to `factor`)."""
         out = {} if out is None else out
-        Sig = out.get("Sig") if out.get("Sig") is not None else self.empty(SYM)
-        x = out.get("x") if out.get("x") is not None else self.empty(VEC)
+        Sig = self._held(out, "Sig", SYM)
+        x = self._held(out, "x", VEC)
         _lib.check(self.lib.mfgm_packed_selinv_mom_s(self.h, -1, _ptr(L), _ptr(S), float(aS), _ptr(y), _ptr(Sig), _ptr(x), None,
                                                      _ptr(self.ws), _stream()), "mfgm_packed_selinv_mom_s")
         return dict(Sig=Sig, x=x)
@@ -437,8 +430,8 @@ class Plan:
         """Backward sweep of a store_G=False factorisation returning dict(Sig, x, klpart): marginals and the per-chain moment-array
         KL sum of `sde_lean(mode=0)` (add log|L_q| - T d / 2), without ever writing the moment array."""
         out = {} if out is None else out
-        Sig = out.get("Sig") if out.get("Sig") is not None else self.empty(SYM)
-        x = out.get("x") if out.get("x") is not None else self.empty(VEC)
+        Sig = self._held(out, "Sig", SYM)
+        x = self._held(out, "x", VEC)
         kl = torch.empty(self.B, dtype=torch.float64, device=self.device)
         _lib.check(self.lib.mfgm_packed_selinv_kl(self.h, -1, _ptr(L), _ptr(S), float(aS), _ptr(y), ctypes.byref(prm), _ptr(Sig), _ptr(x),
                                                   _ptr(kl), _ptr(self.ws), _stream()), "mfgm_packed_selinv_kl")
@@ -481,8 +474,8 @@ class Plan:
         separator system is to be made now, next to this call's level-0 forward sweep: by the second wavefront of the same kernel
         (side=None) or as a kernel of its own on the torch stream `side`."""
         out = {} if out is None else out
-        L = out.get("L") if out.get("L") is not None else self.empty(TRI)
-        y = out.get("y") if out.get("y") is not None else self.empty(VEC)
+        L = self._held(out, "L", TRI)
+        y = self._held(out, "y", VEC)
         self.epoch += 1
         logdet = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
         if not use_ahead and next_sites is None:
@@ -516,10 +509,10 @@ class Plan:
         every producer that writes into a buffer sets it.  Whoever reads (L, y) later passes the marker on."""
         out = {} if out is None else out
         out2 = {} if out2 is None else out2
-        L = out.get("L") if out.get("L") is not None else self.empty(TRI)
-        y = out.get("y") if out.get("y") is not None else self.empty(VEC)
-        L2 = out2.get("L") if out2.get("L") is not None else self.empty(TRI)
-        y2 = out2.get("y") if out2.get("y") is not None else self.empty(VEC)
+        L = self._held(out, "L", TRI)
+        y = self._held(out, "y", VEC)
+        L2 = self._held(out2, "L", TRI)
+        y2 = self._held(out2, "y", VEC)
         self.epoch += 1
         logdet = torch.empty(self.B, dtype=torch.float64, device=self.device) if want_logdet else None
         nxt = cq.struct()
@@ -567,10 +560,7 @@ class Plan:
         the observation nodes are all the ELBO needs.
         thin: the marker of the factor (L, y) (cq_factor_pair); `cq` must then still carry the sites the factor was made with."""
         out = {} if out is None else out
-        Sig = x = None
-        if want_marginals:
-            Sig = out.get("Sig") if out.get("Sig") is not None else self.empty(SYM)
-            x = out.get("x") if out.get("x") is not None else self.empty(VEC)
+        Sig, x = (self._held(out, "Sig", SYM), self._held(out, "x", VEC)) if want_marginals else (None, None)
         kl = torch.empty(self.B, dtype=torch.float64, device=self.device)
         fn, name = (self.lib.mfgm_cq_selinv_kl_thin, "mfgm_cq_selinv_kl_thin") if thin else (self.lib.mfgm_cq_selinv_kl, "mfgm_cq_selinv_kl")
         _lib.check(fn(self.h, int(only_level), ctypes.byref(cq.struct()), _ptr(L), _ptr(y), ctypes.byref(prm), _ptr(Sig),
